@@ -18,6 +18,11 @@ Launch (driver contract):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the K steps and prints the result
+line.  ``--full`` adds the secondary measurement (the direct,
+uncompressed path, reported as ``direct_path``).  ``--dump-outputs DIR``
+writes the spectrum the last timed step produced to ``DIR/fp.npy``.
+
 Data: synthetic epoch-structured PTA (random-init) of the BASELINE
 config shape — there is no network for real datasets.
 """
@@ -157,6 +162,34 @@ def run_step(pta, eng, pool, args, fp_accum):
     return fp_accum
 
 
+#: byte budget of one --dump-outputs directory
+DUMP_MAX_BYTES = 48 * 2 ** 20
+
+
+def dump_outputs(dirname, full):
+    """Write the gathered (D*world, F) fp64 spectrum of the last timed
+    step to ``dirname/fp.npy``.  A spectrum over the byte budget is cut
+    to a fixed, seeded sample of its rows (and, if one row alone is too
+    large, of its columns), in ascending index order, so two builds run
+    with the same arguments dump the same entries."""
+    import os
+
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(20240)
+    nrow, ncol = full.shape
+    max_elems = DUMP_MAX_BYTES // 8
+    if ncol > max_elems:
+        cols = np.sort(rng.choice(ncol, max_elems, replace=False))
+        full = full[:, torch.as_tensor(cols, device=full.device)]
+        ncol = max_elems
+    keep = max(1, max_elems // ncol)
+    if nrow > keep:
+        rows = np.sort(rng.choice(nrow, keep, replace=False))
+        full = full[torch.as_tensor(rows, device=full.device)]
+    arr = full.detach().cpu().numpy().astype(np.float64, copy=False)
+    np.save(os.path.join(dirname, "fp.npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -185,6 +218,12 @@ def main():
                     help="ECORR as block-diagonal white noise (config 4)")
     ap.add_argument("--preset", choices=sorted(PRESETS), default=None,
                     help="BASELINE.json config preset")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the direct (uncompressed) path and "
+                         "report it as direct_path")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's spectrum to "
+                         "DIR/fp.npy (fp64; seeded row sample if large)")
     args = ap.parse_args()
     if args.preset:
         defaults = {a.dest: a.default for a in ap._actions}
@@ -276,12 +315,17 @@ def main():
     finite = bool(torch.isfinite(full).all().item())
     assert finite, "non-finite Fp values in the benchmark spectrum"
 
-    # secondary (untimed-region) measurement: the DIRECT full-m path
-    # with the Schur draw compression off — reported alongside the
-    # compressed headline so both numbers are on record.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, full)
+
+    # secondary (untimed-region) measurement, --full only: the DIRECT
+    # full-m path with the Schur draw compression off — reported
+    # alongside the compressed headline so both numbers are on record
+    # (VERDICT r01).
     direct = None
     if (
-        not args.no_compress
+        args.full
+        and not args.no_compress
         and any(blk.comp is not None for blk in eng.blocks)
         and max(blk.m for blk in eng.blocks) <= 128
     ):

@@ -32,6 +32,54 @@ def test_bench_json_contract():
     assert j["value"] > 0 and j["vs_baseline"] == j["value"] / 6.0
     assert j["config"]["global_batch"] == 4
 
+def test_bench_plain_run_is_lean_and_full_adds_direct_path():
+    """A plain run reports the headline only; the direct-path secondary
+    measurement lives behind --full."""
+    assert "direct_path" not in _run()
+    j = _run("--full")
+    assert j["direct_path"]["value"] > 0
+    assert j["direct_path"]["ms_per_step"] > 0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes the last timed step's spectrum as fp64 .npy,
+    identically from run to run."""
+    import numpy as np
+
+    a_dir, b_dir = tmp_path / "a", tmp_path / "b"
+    j = _run("--dump-outputs", str(a_dir))
+    _run("--dump-outputs", str(b_dir), "--full")
+    a = np.load(a_dir / "fp.npy")
+    b = np.load(b_dir / "fp.npy")
+    assert a.dtype == np.float64
+    assert list(a.shape) == j["config"]["spectrum_shape"]
+    assert np.isfinite(a).all()
+    np.testing.assert_array_equal(a, b)
+
+
+def test_bench_dump_outputs_samples_large_spectrum(tmp_path, monkeypatch):
+    """Over the byte budget the dump is a fixed, seeded, ordered sample."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    full = torch.arange(40 * 6, dtype=torch.float64).reshape(40, 6)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 6 * 8)
+    bench.dump_outputs(str(tmp_path / "a"), full)
+    bench.dump_outputs(str(tmp_path / "b"), full)
+    a = np.load(tmp_path / "a" / "fp.npy")
+    assert a.shape == (10, 6) and a.nbytes <= bench.DUMP_MAX_BYTES
+    np.testing.assert_array_equal(a, np.load(tmp_path / "b" / "fp.npy"))
+    rows = (a[:, 0] / 6).astype(int)
+    assert (np.diff(rows) > 0).all()
+    np.testing.assert_array_equal(a, full.numpy()[rows])
+    # one row alone over the budget: columns are sampled too
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 8)
+    bench.dump_outputs(str(tmp_path / "c"), full)
+    assert np.load(tmp_path / "c" / "fp.npy").shape == (1, 4)
+
+
 def test_bench_presets_parse():
     for p in ("ecorr67", "fp45", "ska200", "nmfp67"):
         j = _run("--preset", p)
