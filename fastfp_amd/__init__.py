@@ -3,7 +3,9 @@
 Brand-new implementation of the capabilities of ``gabefreedman/fastfp``
 (plain and noise-marginalized Fp statistics) designed MI355X-first:
 PyTorch-ROCm fp64 tensors, hand-written HIP/CDNA4 kernels (MFMA fp64
-DGEMM, batched Cholesky, fused triangular-solve + 2x2 Fp reduction) and
+DGEMM, batched Cholesky, fused triangular-solve + 2x2 Fp reduction,
+Fe sky assembly with a fused maximum over the sky — ``FastFe.sweep_max``
+/ ``NMFe.sweep_max``) and
 ``torch.distributed``/RCCL draw- and frequency-sharding over xGMI.
 No JAX, no Triton, no CUDA-compat shims.
 

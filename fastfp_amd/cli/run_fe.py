@@ -12,6 +12,12 @@ the (frequency x sky) grid and writes ``{savefile}.json``:
 The sky grid is an equal-area-ish lattice of ``--nsky`` points
 (Fibonacci sphere), or a single ``--theta/--phi`` location.  Pulsars
 must carry sky positions (``PulsarData.pos``).
+
+``--skymax`` writes the statistic maximised over the sky instead of the
+map: ``{savefile}.max.npy`` (nfreqs,) and ``{savefile}.argmax.npy``
+(indices into ``sky``); ``{savefile}.json`` then holds only the
+``freqs`` and ``sky`` axes.  ``--assemble device`` runs the sky
+assembly of the map in the HIP kernel (GPU only).
 """
 
 import argparse
@@ -57,6 +63,8 @@ def main(
     device=None,
     rn_comps=30,
     gwb_comps=30,
+    skymax=False,
+    assemble="host",
 ):
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.INFO)
     logger = logging.getLogger(__name__)
@@ -96,7 +104,36 @@ def main(
 
     t0 = time.perf_counter()
     fe = FastFe(psrs, pta)
-    local = fe.sweep(freqs, local_sky, Nvecs, Ts, sigmas, device=dev) \
+    if skymax:
+        # per-rank maximum over its sky shard, then the maximum over
+        # ranks (shards are in sky order: the first maximum is the
+        # lowest sky index)
+        if local_sky:
+            fm, am = fe.sweep_max(freqs, local_sky, Nvecs, Ts, sigmas,
+                                  device=dev)
+        else:
+            fm = np.full(nfreqs, -np.inf)
+            am = np.zeros(nfreqs, dtype=np.int64)
+        am = am + (shard_slice(len(sky), rank, world).start or 0)
+        fms = all_gather_concat(
+            torch.as_tensor(fm[None], dtype=torch.float64), world, dim=0
+        ).numpy()
+        ams = all_gather_concat(
+            torch.as_tensor(am[None], dtype=torch.int64), world, dim=0
+        ).numpy()
+        logger.info(f"Fe-statistic wall time: {time.perf_counter() - t0:.4f} s")
+        if rank == 0:
+            best = np.argmax(fms, axis=0)
+            cols = np.arange(nfreqs)
+            np.save(f"{savefile}.max.npy", fms[best, cols])
+            np.save(f"{savefile}.argmax.npy", ams[best, cols])
+            with open(f"{savefile}.json", "w") as f:
+                json.dump({"freqs": [float(x) for x in freqs],
+                           "sky": [[t, p] for t, p in sky]}, f)
+        cleanup()
+        return
+    local = fe.sweep(freqs, local_sky, Nvecs, Ts, sigmas, device=dev,
+                     assemble=assemble) \
         if local_sky else np.zeros((0, nfreqs))
     t_local = torch.as_tensor(local, dtype=torch.float64)
     full = all_gather_concat(t_local, world, dim=0).numpy()
@@ -131,6 +168,12 @@ def cli():
     parser.add_argument("--device", type=str, default=None)
     parser.add_argument("--rn_comps", type=int, default=30)
     parser.add_argument("--gwb_comps", type=int, default=30)
+    parser.add_argument("--skymax", action="store_true",
+                        help="write the sky-maximised Fe (.max.npy / "
+                             ".argmax.npy) instead of the (sky x freq) map")
+    parser.add_argument("--assemble", choices=["host", "device"],
+                        default="host",
+                        help="where the sky assembly of the map runs")
     main(**vars(parser.parse_args()))
 
 

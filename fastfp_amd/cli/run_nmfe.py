@@ -7,6 +7,11 @@ noisefile, chainfile, savefile; 25% burn-in, last 4 bookkeeping
 columns stripped); the sky grid mirrors ``run_fe``.  Output:
 ``{outdir}/{savefile}.npy`` of shape (nsamples, nsky, nfreqs) plus
 ``{outdir}/{savefile}.meta.json`` with the freqs/sky axes.
+
+``--skymax`` writes the sky-maximised statistic instead of the cube:
+``{savefile}.max.npy`` (nsamples, nfreqs) and ``{savefile}.argmax.npy``
+(indices into the meta JSON's ``sky`` list).  ``--assemble device``
+runs the sky assembly of the cube in the HIP kernel (GPU only).
 """
 
 import argparse
@@ -20,6 +25,7 @@ import torch
 
 from fastfp_amd.cli.run_fe import fibonacci_sky
 from fastfp_amd.data import get_tspan, load_pulsars
+from fastfp_amd.engine import FpEngine
 from fastfp_amd.festat import NMFe
 from fastfp_amd.model import get_mats_nmfp, initialize_pta
 from fastfp_amd.parallel import (
@@ -47,6 +53,8 @@ def main(
     device=None,
     seed=0,
     batch_size=64,
+    skymax=False,
+    assemble="host",
 ):
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.INFO)
     logger = logging.getLogger(__name__)
@@ -96,19 +104,36 @@ def main(
 
     t0 = time.perf_counter()
     nm = NMFe(psrs, pta.rn_containers)
-    parts = []
+    # ONE engine for every batch: the frequency precompute does not
+    # depend on the draws
+    engine = None
+    if len(my_idx):
+        engine = FpEngine(psrs, Nvecs, Ts, device=dev)
+        engine.precompute(freqs)
+    parts, parts_arg = [], []
     for lo in range(0, len(my_idx), batch_size):
         sel = my_idx[lo : lo + batch_size]
         samples = {
             p: rns_full[ct, sel] for ct, p in enumerate(pta.params)
         }
-        parts.append(nm.sweep(freqs, sky, samples, Nvecs, Ts, device=dev))
-    local = (
-        np.concatenate(parts, axis=0) if parts
-        else np.zeros((0, len(sky), ncwfreqs))
-    )
+        if skymax:
+            fm, am = nm.sweep_max(freqs, sky, samples, Nvecs, Ts,
+                                  device=dev, engine=engine)
+            parts.append(fm)
+            parts_arg.append(am)
+        else:
+            parts.append(nm.sweep(freqs, sky, samples, Nvecs, Ts, device=dev,
+                                  engine=engine, assemble=assemble))
+    tail = (ncwfreqs,) if skymax else (len(sky), ncwfreqs)
+    local = np.concatenate(parts, axis=0) if parts else np.zeros((0,) + tail)
     t_local = torch.as_tensor(local, dtype=torch.float64)
     full = all_gather_concat(t_local, world, dim=0).numpy()
+    if skymax:
+        local_arg = (np.concatenate(parts_arg, axis=0) if parts_arg
+                     else np.zeros((0, ncwfreqs), dtype=np.int64))
+        full_arg = all_gather_concat(
+            torch.as_tensor(local_arg, dtype=torch.int64), world, dim=0
+        ).numpy()
     logger.info(
         "Noise marginalized Fe-statistic wall time: "
         f"{time.perf_counter() - t0:.2f} s"
@@ -116,8 +141,15 @@ def main(
 
     if rank == 0:
         os.makedirs(outdir, exist_ok=True)
-        with open(os.path.join(outdir, f"{savefile}.npy"), "wb") as f:
-            np.save(f, full)
+        if skymax:
+            with open(os.path.join(outdir, f"{savefile}.max.npy"), "wb") as f:
+                np.save(f, full)
+            with open(os.path.join(outdir, f"{savefile}.argmax.npy"),
+                      "wb") as f:
+                np.save(f, full_arg)
+        else:
+            with open(os.path.join(outdir, f"{savefile}.npy"), "wb") as f:
+                np.save(f, full)
         with open(os.path.join(outdir, f"{savefile}.meta.json"), "w") as f:
             json.dump({"freqs": [float(x) for x in freqs],
                        "sky": [[t, p] for t, p in sky]}, f)
@@ -143,6 +175,12 @@ def cli():
     parser.add_argument("--device", type=str, default=None)
     parser.add_argument("--seed", type=int, default=0)
     parser.add_argument("--batch_size", type=int, default=64)
+    parser.add_argument("--skymax", action="store_true",
+                        help="write the sky-maximised Fe (.max.npy / "
+                             ".argmax.npy) instead of the full cube")
+    parser.add_argument("--assemble", choices=["host", "device"],
+                        default="host",
+                        help="where the sky assembly of the cube runs")
     main(**vars(parser.parse_args()))
 
 

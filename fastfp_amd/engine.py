@@ -864,6 +864,51 @@ class FpEngine:
                 "dmf,dm->df", Wc, wu)
         return out[:, 0] if not batched else out
 
+    def sweep_products_hip(self, phiinvs, draw_chunk: int = 32) -> torch.Tensor:
+        """:meth:`sweep_products` on the HIP solve: the same five
+        corrected products, stored un-collapsed by the products mode of
+        the trsm kernel.
+
+        ``phiinvs``: per-pulsar (m,) or (D, m) diagonal phi^-1; returns
+        the (P, 5, F) / (P, D, 5, F) device tensor.  When every pulsar
+        shares one basis size with ``pad16(m) <= 128`` this is ONE
+        ``chol_batch`` and ONE ``trsm_prods`` launch per draw chunk
+        across all pulsars, on the direct (uncompressed) system.
+        Otherwise (CPU/eager engine, ragged bases, larger m) it returns
+        ``self.sweep_products(phiinvs=...)``."""
+        assert self.freqs is not None, "call precompute(freqs) first"
+        from fastfp_amd import ops
+
+        st = getattr(self, "_direct_stack", None)
+        if st is None or ops.pad16(st["TNT"].shape[-1]) > ops.MAX_MP_CHOL:
+            return self.sweep_products(phiinvs=phiinvs)
+        from fastfp_amd.ops import _fastfp_hip as ext
+
+        F = self.freqs.shape[0]
+        P = len(self.blocks)
+        mp = ops.pad16(st["TNT"].shape[-1])
+        pin = [_t64(p, self.device) for p in phiinvs]
+        batched = pin[0].dim() == 2
+        pinv_all = torch.stack(
+            [p if batched else p[None, :] for p in pin])  # (P, D, m)
+        D = pinv_all.shape[1]
+        out = torch.empty((P, D, 5, F), dtype=torch.float64,
+                          device=self.device)
+        for lo in range(0, D, draw_chunk):
+            hi = min(lo + draw_chunk, D)
+            L, invd = ext.chol_batch(
+                st["TNT"], pinv_all[:, lo:hi, :].contiguous(), mp)
+            if lo == 0 and hi == D:
+                ext.trsm_prods(L, invd, st["RHS"], st["sNs"], st["sNr"],
+                               out, 1.0)
+            else:  # a draw slice of `out` is not contiguous
+                part = torch.empty((P, hi - lo, 5, F), dtype=torch.float64,
+                                   device=self.device)
+                ext.trsm_prods(L, invd, st["RHS"], st["sNs"], st["sNr"],
+                               part, 1.0)
+                out[:, lo:hi] = part
+        return out if batched else out[:, 0]
+
     def _accum_eager(self, blk: PulsarBlock, sigma, fp_out):
         """Eager per-pulsar accumulation: Cholesky + TRSM + fused 2x2."""
         self._accum_eager_mats(sigma, blk.RHS, blk.sNs, blk.sNr, fp_out, 1.0)

@@ -25,6 +25,14 @@ same quantities the Fp kernels reduce), and any number of sky
 locations costs only an O(P) 4x4 assembly each.  A full (sky x freq)
 Fe map is therefore nearly free on top of an Fp sweep — the
 MI355X-native restructure of the statistic.
+
+Two assemblies exist.  The default (``assemble="host"``) takes the
+products from the torch path and solves the 4x4 systems in numpy.  On a
+HIP engine ``assemble="device"`` and ``sweep_max`` take the products
+from the HIP solve (``FpEngine.sweep_products_hip``) and run the sky
+assembly in the MFMA kernels ``ops.fe_assemble`` / ``ops.fe_skymax``;
+``sweep_max`` returns the statistic maximised over the sky with its
+argmax and never forms the (draws x sky x freqs) cube.
 """
 
 from __future__ import annotations
@@ -34,7 +42,7 @@ import math
 import numpy as np
 import torch
 
-from fastfp_amd.engine import FpEngine
+from fastfp_amd.engine import FpEngine, _t64
 from fastfp_amd.xcy import get_xCy
 
 
@@ -111,6 +119,54 @@ def _assemble_fe(prods, fplus, fcross, rcond=1e-12):
     return 0.5 * np.einsum("fi,fi->f", N, x)
 
 
+def _check_assemble(assemble, device, engine):
+    """Validate the ``assemble=`` keyword and resolve the default
+    device.  ``"device"`` needs a HIP engine: a CPU device (or a CPU
+    engine) is rejected before any precompute runs."""
+    if assemble not in ("host", "device"):
+        raise ValueError(
+            f"assemble must be 'host' or 'device', got {assemble!r}")
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    if assemble == "device":
+        dev = engine.device if engine is not None else torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError(
+                "assemble='device' runs the sky assembly in the HIP "
+                f"kernels and needs a GPU engine (got device {dev}); use "
+                "assemble='host' on the CPU")
+    return device
+
+
+def _require_hip_engine(engine):
+    if not engine._use_hip:
+        raise ValueError(
+            "assemble='device' needs an engine on the HIP path "
+            "(force_eager engines have no HIP products)")
+
+
+def _phiinvs_from_sigmas(engine, sigmas):
+    """Fixed-noise (m, m) sigmas -> per-pulsar diagonal phi^-1 (the
+    ``get_mats_fp`` contract sigma = TNT + diag(phi^-1), as in
+    ``FpEngine.sweep``)."""
+    out = []
+    for blk, sg in zip(engine.blocks, sigmas):
+        sg = _t64(sg, engine.device)
+        out.append((torch.diagonal(sg) - torch.diagonal(blk.TNT)).contiguous())
+    return out
+
+
+def _antenna_table(pos, sky, device=None):
+    """(nsky, P, 2) = [F+, Fx] of every pulsar toward every sky point;
+    a numpy array, or an fp64 tensor on ``device``."""
+    ant = np.empty((len(sky), pos.shape[0], 2))
+    for k, (gwtheta, gwphi) in enumerate(sky):
+        ant[k, :, 0], ant[k, :, 1] = gw_antenna_pattern(pos, gwtheta, gwphi)
+    if device is None:
+        return ant
+    return torch.as_tensor(ant, dtype=torch.float64).to(device)
+
+
 class FastFe:
     """Fe detection statistic over (frequency, sky).
 
@@ -167,6 +223,7 @@ class FastFe:
         device: str = None,
         freq_chunk: int = 2048,
         engine: FpEngine = None,
+        assemble: str = "host",
     ) -> np.ndarray:
         """Fe over ``freqs`` x ``sky`` (list of (gwtheta, gwphi)).
 
@@ -174,12 +231,25 @@ class FastFe:
         computed once on the engine (GPU precompute kernels + one
         m-dim solve per pulsar); each sky point is then an O(P) 4x4
         assembly per frequency.
+
+        ``assemble="device"`` (HIP engines only) takes the products
+        from the HIP solve and runs the sky assembly in the
+        ``fe_assemble`` kernel; the default ``"host"`` is the numpy
+        assembly.
         """
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
+        device = _check_assemble(assemble, device, engine)
         if engine is None:
             engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
             engine.precompute(freqs, freq_chunk=freq_chunk)
+        if assemble == "device":
+            from fastfp_amd import ops
+
+            _require_hip_engine(engine)
+            prods = engine.sweep_products_hip(
+                _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
+            fe = ops.fe_assemble(prods[:, None].contiguous(),
+                                 _antenna_table(self.pos, sky, engine.device))
+            return fe[0].cpu().numpy()
         prods = engine.sweep_products(sigmas=sigmas)  # (P, 5, F) tensor
         prods = prods.cpu().numpy()
         out = np.empty((len(sky), prods.shape[2]))
@@ -187,6 +257,43 @@ class FastFe:
             fplus, fcross = gw_antenna_pattern(self.pos, gwtheta, gwphi)
             out[k] = _assemble_fe(prods, fplus, fcross)
         return out
+
+    def sweep_max(
+        self,
+        freqs,
+        sky,
+        Nvecs,
+        Ts,
+        sigmas,
+        device: str = None,
+        engine: FpEngine = None,
+    ):
+        """Fe maximised over ``sky`` per frequency.
+
+        Returns ``(femax (F,), argmax (F,))``; ``argmax`` indexes into
+        ``sky``.  On a HIP engine the products come from the HIP solve
+        and the ``fe_skymax`` kernel keeps the running maximum, so only
+        (F,)-sized results leave the device; on a CPU engine this is the
+        host assembly followed by ``np.nanmax`` / ``np.nanargmax`` (the
+        reference implementation).
+        """
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        if engine is None:
+            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
+            engine.precompute(freqs)
+        if engine._use_hip:
+            from fastfp_amd import ops
+
+            prods = engine.sweep_products_hip(
+                _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
+            femax, argmax, _ = ops.fe_skymax(
+                prods[:, None].contiguous(),
+                _antenna_table(self.pos, sky, engine.device))
+            return (femax[0].cpu().numpy(),
+                    argmax[0].cpu().numpy().astype(np.int64))
+        grid = self.sweep(freqs, sky, Nvecs, Ts, sigmas, engine=engine)
+        return np.nanmax(grid, axis=0), np.nanargmax(grid, axis=0)
 
 
 def compute_Fe(psrs, pta, noise, freqs, sky, device=None) -> np.ndarray:
@@ -257,14 +364,19 @@ class NMFe:
         draw_chunk: int = 128,
         freq_chunk: int = 2048,
         engine: FpEngine = None,
+        assemble: str = "host",
     ) -> np.ndarray:
         """Fe over (draws x sky x freqs).  ``samples``: parameter-name
         -> (D,) arrays (the ``map_params`` format).  Returns
-        (D, nsky, F)."""
+        (D, nsky, F).
+
+        ``assemble="device"`` (HIP engines only): products from the HIP
+        solve, sky assembly in the ``fe_assemble`` kernel; only the
+        finished map is copied to the host.  The default ``"host"`` is
+        the numpy assembly."""
         from fastfp_amd.noise import batch_phiinv
 
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
+        device = _check_assemble(assemble, device, engine)
         if engine is None:
             engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
             engine.precompute(freqs, freq_chunk=freq_chunk)
@@ -272,6 +384,18 @@ class NMFe:
         phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
         D = phiinvs[0].shape[0]
         F = engine.freqs.shape[0]
+        if assemble == "device":
+            from fastfp_amd import ops
+
+            _require_hip_engine(engine)
+            ant_d = _antenna_table(self.fe.pos, sky, engine.device)
+            out = np.empty((D, len(sky), F))
+            for lo in range(0, D, draw_chunk):
+                hi = min(lo + draw_chunk, D)
+                prods = engine.sweep_products_hip(
+                    [p[lo:hi] for p in phiinvs])  # (P, Dc, 5, F)
+                out[lo:hi] = ops.fe_assemble(prods, ant_d).cpu().numpy()
+            return out
         ant = [gw_antenna_pattern(self.fe.pos, th, ph) for th, ph in sky]
         out = np.empty((D, len(sky), F))
         for lo in range(0, D, draw_chunk):
@@ -282,3 +406,61 @@ class NMFe:
             for k, (fplus, fcross) in enumerate(ant):
                 out[lo:hi, k, :] = _assemble_fe_draws(prods, fplus, fcross)
         return out
+
+    def sweep_max(
+        self,
+        freqs,
+        sky,
+        samples: dict,
+        Nvecs,
+        Ts,
+        device: str = None,
+        draw_chunk: int = 128,
+        engine: FpEngine = None,
+    ):
+        """Fe maximised over ``sky`` for every (draw, frequency).
+
+        Returns ``(femax (D, F), argmax (D, F))``; ``argmax`` indexes
+        into ``sky``.  The (D, nsky, F) cube is never formed: on a HIP
+        engine each draw chunk goes products (HIP solve) ->
+        ``fe_skymax`` kernel and only (Dc, F)-sized results leave the
+        device; on a CPU engine each chunk is assembled on the host and
+        reduced with ``np.nanmax`` / ``np.nanargmax`` (the reference
+        implementation).
+        """
+        from fastfp_amd.noise import batch_phiinv
+
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        if engine is None:
+            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
+            engine.precompute(freqs)
+        phiinvs = batch_phiinv(self.rn_sigs, samples)
+        phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
+        D = phiinvs[0].shape[0]
+        F = engine.freqs.shape[0]
+        femax = np.empty((D, F))
+        argmax = np.empty((D, F), dtype=np.int64)
+        if engine._use_hip:
+            from fastfp_amd import ops
+
+            ant_d = _antenna_table(self.fe.pos, sky, engine.device)
+        else:
+            ant = _antenna_table(self.fe.pos, sky)
+        for lo in range(0, D, draw_chunk):
+            hi = min(lo + draw_chunk, D)
+            chunk = [p[lo:hi] for p in phiinvs]
+            if engine._use_hip:
+                prods = engine.sweep_products_hip(chunk)  # (P, Dc, 5, F)
+                fm, am, _ = ops.fe_skymax(prods, ant_d)
+                femax[lo:hi] = fm.cpu().numpy()
+                argmax[lo:hi] = am.cpu().numpy()
+            else:
+                prods = engine.sweep_products(phiinvs=chunk).cpu().numpy()
+                cube = np.stack([
+                    _assemble_fe_draws(prods, ant[k, :, 0], ant[k, :, 1])
+                    for k in range(len(sky))
+                ])  # (nsky, Dc, F)
+                femax[lo:hi] = np.nanmax(cube, axis=0)
+                argmax[lo:hi] = np.nanargmax(cube, axis=0)
+        return femax, argmax

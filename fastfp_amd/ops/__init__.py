@@ -189,3 +189,87 @@ def chol_trsm_fp_accum(TNT, phiinv, RHS, sNs, sNr, fp_out, gsign=1.0):
         L[:, idx, idx] = 1.0
         invd = ext.diag_inv(L.contiguous())
     ext.trsm_fp_accum(L, invd, RHS, sNs, sNr, fp_out, gsign)
+
+
+# ----------------------------------------------------------------------
+# Fe sky assembly (fe_kernels.hip)
+# ----------------------------------------------------------------------
+def _fe_ext():
+    require_hip()
+    ext = _try_load()
+    if ext is None:
+        raise RuntimeError(
+            "the Fe sky-assembly kernels need the HIP extension "
+            f"(_fastfp_hip); import error: {_load_err}"
+        )
+    return ext
+
+
+def fe_assemble(prods, ant, repair: bool = True):
+    """Fe over (draw, sky, frequency) on the device.
+
+    ``prods`` (P, D, 5, F) = [ss, cc, sc, sr, cr] and ``ant``
+    (nsky, P, 2) = [F+, Fx], both fp64 device tensors.  Returns the
+    (D, nsky, F) device tensor.
+
+    The kernel solves each point's 4x4 system by Cholesky in registers
+    and writes NaN where a pivot is degenerate (``s_j <= 1e-12 M_jj``
+    or non-finite).  With ``repair`` those entries are recomputed on the
+    host through ``festat._assemble_fe_draws`` (pseudo-inverse branch);
+    the common path costs one ``.any()`` sync.
+    """
+    ext = _fe_ext()
+    fe = ext.fe_assemble(prods.contiguous(), ant.contiguous())
+    if not repair:
+        return fe
+    bad = torch.isnan(fe)
+    if bool(bad.any()):
+        from fastfp_amd.festat import _assemble_fe_draws
+
+        prods_h = prods.cpu().numpy()
+        ant_h = ant.cpu().numpy()
+        for k in torch.nonzero(bad.any(dim=2).any(dim=0)).flatten().tolist():
+            full = torch.as_tensor(
+                _assemble_fe_draws(prods_h, ant_h[k, :, 0], ant_h[k, :, 1]),
+                dtype=fe.dtype,
+            ).to(fe.device)  # (D, F)
+            fe[:, k, :] = torch.where(bad[:, k, :], full, fe[:, k, :])
+    return fe
+
+
+def fe_skymax(prods, ant, repair: bool = True):
+    """Fe maximised over the sky, fused in the kernel: nothing of size
+    nsky x D x F is written.
+
+    Returns ``(femax (D, F) f64, argmax (D, F) int32, nskip (D, F)
+    int32)`` device tensors; ``argmax`` indexes the rows of ``ant`` (the
+    lowest index on ties) and ``nskip`` counts the degenerate points the
+    kernel left out of the maximum.  With ``repair`` every (d, f) column
+    with ``nskip > 0`` is recomputed on the host over ALL sky points
+    through ``festat._assemble_fe_draws`` (rare; the common path costs
+    one ``.any()`` sync).  ``nskip`` keeps the kernel's counts.
+    """
+    ext = _fe_ext()
+    femax, argmax, nskip = ext.fe_skymax(prods.contiguous(), ant.contiguous())
+    if not repair:
+        return femax, argmax, nskip
+    bad = nskip > 0
+    if bool(bad.any()):
+        import numpy as np
+
+        from fastfp_amd.festat import _assemble_fe_draws
+
+        d_idx, f_idx = torch.nonzero(bad, as_tuple=True)
+        # the bad columns as a (P, ncols, 5, 1) product set
+        sub = prods[:, d_idx, :, f_idx]  # (ncols, P, 5)
+        sub_h = sub.permute(1, 0, 2).unsqueeze(-1).cpu().numpy()
+        ant_h = ant.cpu().numpy()
+        vals = np.stack([
+            _assemble_fe_draws(sub_h, ant_h[k, :, 0], ant_h[k, :, 1])[:, 0]
+            for k in range(ant_h.shape[0])
+        ])  # (nsky, ncols)
+        femax[d_idx, f_idx] = torch.as_tensor(
+            np.nanmax(vals, axis=0), dtype=femax.dtype).to(femax.device)
+        argmax[d_idx, f_idx] = torch.as_tensor(
+            np.nanargmax(vals, axis=0), dtype=argmax.dtype).to(argmax.device)
+    return femax, argmax, nskip

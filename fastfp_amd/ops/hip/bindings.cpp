@@ -23,6 +23,14 @@ void launch_sigdots_block(const double*, const double*, const double*,
                           const long*, int, int, int, double*, double*,
                           hipStream_t);
 void launch_diag_inv(const double*, int, long, double*, hipStream_t);
+void launch_trsm_prods(const double*, const double*, const double*,
+                       const double*, const double*, int, int, int, int,
+                       double, double*, hipStream_t);
+int fe_max_pulsars();
+int launch_fe_assemble(const double*, const double*, int, int, int, int,
+                       double*, hipStream_t);
+int launch_fe_skymax(const double*, const double*, int, int, int, int,
+                     double*, int*, int*, hipStream_t);
 }
 
 namespace {
@@ -154,6 +162,105 @@ void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                  fp.data_ptr<double>(), stream());
 }
 
+// trsm_prods: the same solve as trsm_fp_accum, but the five corrected
+// products [ss, cc, sc, sr, cr] are stored un-collapsed: out (D,5,F)
+// for a single pulsar, (P,D,5,F) pulsar-batched.  Plain stores — `out`
+// need not be zeroed.
+void trsm_prods(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
+                torch::Tensor sNs, torch::Tensor sNr, torch::Tensor out,
+                double gsign) {
+  check_f64(L, "L");
+  check_f64(invd, "invd");
+  check_f64(RHS, "RHS");
+  check_f64(sNs, "sNs");
+  check_f64(sNr, "sNr");
+  check_f64(out, "out");
+  const bool batched = RHS.dim() == 3;
+  const int P = batched ? RHS.size(0) : 1;
+  const int mp = L.size(1);
+  const int F = sNs.size(batched ? 2 : 1);
+  TORCH_CHECK(out.dim() == (batched ? 4 : 3), "out rank");
+  const int D = out.size(batched ? 1 : 0);
+  TORCH_CHECK(L.dim() == 3 && L.size(2) == mp && L.size(0) == (long)P * D,
+              "L batch != P*D");
+  TORCH_CHECK(invd.numel() == (long)P * D * mp * 16, "invd shape");
+  TORCH_CHECK(RHS.size(batched ? 1 : 0) == mp &&
+                  RHS.size(batched ? 2 : 1) == 2 * F + 1,
+              "RHS shape");
+  TORCH_CHECK(sNs.numel() == (long)P * 3 * F && sNr.numel() == (long)P * 2 * F,
+              "sNs/sNr shape");
+  TORCH_CHECK((!batched || out.size(0) == P) &&
+                  out.size(batched ? 2 : 1) == 5 &&
+                  out.size(batched ? 3 : 2) == F,
+              "out shape");
+  TORCH_CHECK(mp % 16 == 0 && mp >= 16 && mp <= 128,
+              "trsm_prods supports a padded solve dimension mp <= 128 "
+              "(multiple of 16); got mp=", mp,
+              " — use FpEngine.sweep_products for larger bases");
+  if (D == 0 || F == 0) return;
+  launch_trsm_prods(L.data_ptr<double>(), invd.data_ptr<double>(),
+                    RHS.data_ptr<double>(), sNs.data_ptr<double>(),
+                    sNr.data_ptr<double>(), mp, F, D, P, gsign,
+                    out.data_ptr<double>(), stream());
+}
+
+namespace {
+
+void check_fe_inputs(const torch::Tensor& prods, const torch::Tensor& ant) {
+  check_f64(prods, "prods");
+  check_f64(ant, "ant");
+  TORCH_CHECK(prods.dim() == 4 && prods.size(2) == 5,
+              "prods must be (P, D, 5, F)");
+  TORCH_CHECK(ant.dim() == 3 && ant.size(2) == 2 &&
+                  ant.size(1) == prods.size(0),
+              "ant must be (nsky, P, 2) with P matching prods");
+  TORCH_CHECK(ant.device() == prods.device(), "prods/ant device mismatch");
+  TORCH_CHECK(prods.size(0) >= 1 && prods.size(0) <= fe_max_pulsars(),
+              "the Fe sky kernels keep a (5, P, 16) product tile in LDS and "
+              "support 1 <= P <= ", fe_max_pulsars(), " pulsars; got P=",
+              prods.size(0));
+  TORCH_CHECK(prods.size(3) < (1L << 31) && ant.size(0) < (1L << 31) &&
+                  prods.size(1) < (1L << 31),
+              "dimension overflow");
+}
+
+}  // namespace
+
+// fe_assemble: prods (P,D,5,F), ant (nsky,P,2) -> fe (D,nsky,F); NaN at
+// points whose 4x4 M has a degenerate Cholesky pivot.
+torch::Tensor fe_assemble(torch::Tensor prods, torch::Tensor ant) {
+  check_fe_inputs(prods, ant);
+  const int P = prods.size(0), D = prods.size(1), F = prods.size(3);
+  const int nsky = ant.size(0);
+  auto fe = torch::empty({D, nsky, F}, prods.options());
+  const int err = launch_fe_assemble(prods.data_ptr<double>(),
+                                     ant.data_ptr<double>(), P, D, F, nsky,
+                                     fe.data_ptr<double>(), stream());
+  TORCH_CHECK(err == 0, "fe_assemble launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  return fe;
+}
+
+// fe_skymax: running maximum over the sky inside the kernel ->
+// femax (D,F) f64, argmax (D,F) i32 (lowest index on ties, -1 if every
+// point was skipped), nskip (D,F) i32 = degenerate points left out.
+std::vector<torch::Tensor> fe_skymax(torch::Tensor prods, torch::Tensor ant) {
+  check_fe_inputs(prods, ant);
+  const int P = prods.size(0), D = prods.size(1), F = prods.size(3);
+  const int nsky = ant.size(0);
+  auto iopts = prods.options().dtype(torch::kInt32);
+  auto femax = torch::full({D, F}, -INFINITY, prods.options());
+  auto argmax = torch::full({D, F}, -1, iopts);
+  auto nskip = torch::zeros({D, F}, iopts);
+  const int err = launch_fe_skymax(
+      prods.data_ptr<double>(), ant.data_ptr<double>(), P, D, F, nsky,
+      femax.data_ptr<double>(), argmax.data_ptr<int>(),
+      nskip.data_ptr<int>(), stream());
+  TORCH_CHECK(err == 0, "fe_skymax launch failed: ",
+              hipGetErrorString((hipError_t)err));
+  return {femax, argmax, nskip};
+}
+
 // diag_inv: invert the 16x16 diagonal blocks of batched lower-tri L
 // (B, mp, mp) -> invd (B, mp/16, 16, 16); the m > 128 direct path.
 torch::Tensor diag_inv(torch::Tensor L) {
@@ -207,4 +314,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "chol_batch into caller-owned L/invd (pipeline buffers)");
   m.def("trsm_fp_accum", &trsm_fp_accum,
         "batched TRSM + fused 2x2 Fp reduction");
+  m.def("trsm_prods", &trsm_prods,
+        "batched TRSM storing the five corrected products (Fe input)");
+  m.def("fe_assemble", &fe_assemble,
+        "Fe sky assembly: MFMA pulsar sums + in-register 4x4 solve");
+  m.def("fe_skymax", &fe_skymax,
+        "Fe sky assembly fused with the maximum over sky points");
 }

@@ -607,14 +607,20 @@ __global__ __launch_bounds__(256) void chol_wave_kernel(
 // across ~D consecutive blocks) instead of streaming 16 different
 // strips — A/B arm for the measured 2.9 ms RHS-load attribution
 // (FASTFP_TRSM_GRID=d).
-template <int NBT, int DPG, bool SWAP = false>
+// PRODS: products mode for the sky-coherent Fe statistic — the
+// epilogue stores the five corrected products [M11, M22, M12, N1, N2]
+// = [s|s, c|c, s|c, s|r, c|r] un-collapsed into
+// out[((p*D + d)*5 + i)*F + f] (plain stores, no accumulation) instead
+// of reducing them to Fp.
+template <int NBT, int DPG, bool SWAP = false, bool PRODS = false>
 __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
     const double* __restrict__ L_all /*(P*D,mp,mp)*/,
     const double* __restrict__ invd_all /*(P*D, mp/16, 16, 16)*/,
     const double* __restrict__ RHS_all /*(P, mp, 2F+1)*/,
     const double* __restrict__ sNs_all /*(P,3,F)*/,
     const double* __restrict__ sNr_all /*(P,2,F)*/, int F, int D,
-    double gsign, double* __restrict__ fp_all /*(P,D,F)*/) {
+    double gsign,
+    double* __restrict__ fp_all /*(P,D,F); PRODS: (P,D,5,F)*/) {
   // grid.z batches PULSARS (one launch per draw chunk); each pulsar
   // accumulates into its own fp plane, summed deterministically by the
   // caller (no cross-pulsar races, no atomics).
@@ -796,10 +802,19 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
       const double M12 = sNs[2 * F + f] - gsign * a3;
       const double N1 = sNr[f] - gsign * a2;
       const double N2 = sNr[F + f] - gsign * b2;
-      const double det = fma(M11, M22, -M12 * M12);
-      const double num =
-          fma(N1 * N1, M22, fma(-2.0 * N1, N2 * M12, N2 * N2 * M11));
-      fp[(long)(d0 + e) * F + f] += 0.5 * num / det;
+      if constexpr (PRODS) {
+        double* o = fp_all + (((long)pp * D + (d0 + e)) * 5) * F + f;
+        o[0] = M11;
+        o[F] = M22;
+        o[2L * F] = M12;
+        o[3L * F] = N1;
+        o[4L * F] = N2;
+      } else {
+        const double det = fma(M11, M22, -M12 * M12);
+        const double num =
+            fma(N1 * N1, M22, fma(-2.0 * N1, N2 * M12, N2 * N2 * M11));
+        fp[(long)(d0 + e) * F + f] += 0.5 * num / det;
+      }
     }
   }
 }
@@ -1442,6 +1457,27 @@ void launch_trsm_fp(const double* L, const double* invd, const double* RHS,
       TRSM_BIG_CASE(13) TRSM_BIG_CASE(14) TRSM_BIG_CASE(15) TRSM_BIG_CASE(16)
 #undef TRSM_BIG_CASE
     }
+  }
+}
+
+// Products mode (Fe): one launch over (ftiles, D, P), mp <= 128.  No
+// A/B environment switches — there is one arm.
+void launch_trsm_prods(const double* L, const double* invd, const double* RHS,
+                       const double* sNs, const double* sNr, int mp, int F,
+                       int D, int P, double gsign, double* out,
+                       hipStream_t stream) {
+  const int ftiles = (F + FPT_FREQS - 1) / FPT_FREQS;
+  const dim3 blk(512);
+  const dim3 grid(ftiles, D, P);
+  switch (mp >> 4) {
+#define TRSM_PRODS_CASE(NBT) \
+    case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1, false, true>), grid, \
+                  blk, 0, stream, L, invd, RHS, sNs, sNr, F, D, gsign, out); \
+      break;
+    TRSM_PRODS_CASE(1) TRSM_PRODS_CASE(2) TRSM_PRODS_CASE(3)
+    TRSM_PRODS_CASE(4) TRSM_PRODS_CASE(5) TRSM_PRODS_CASE(6)
+    TRSM_PRODS_CASE(7) TRSM_PRODS_CASE(8)
+#undef TRSM_PRODS_CASE
   }
 }
 

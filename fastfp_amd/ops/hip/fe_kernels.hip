@@ -1,0 +1,313 @@
+// fastfp_amd Fe sky-assembly kernels for AMD Instinct MI355X (gfx950).
+//
+// Input: the five corrected per-pulsar products
+//   prods (P, D, 5, F) = [ss, cc, sc, sr, cr]   (trsm_prods output)
+// and the antenna table ant (nsky, P, 2) = [F+, Fx].  Per (sky, draw,
+// frequency) point the Fe statistic needs 13 sums over pulsars,
+//   M = sum_p {F+^2, F+Fx, Fx^2} x {ss, sc, cc}   (10 distinct entries)
+//   N = sum_p {F+, Fx} x {sr, cr}
+// then Fe = 1/2 N^T M^-1 N (4x4).  The sums are a small GEMM with K = P:
+// rows = sky points, columns = flattened (d, f), so they run on
+// v_mfma_f64_16x16x4f64 with P zero-padded to a multiple of 4.
+//
+// Layout (same as trsm_fp_kernel, tools/mfma_probe.hip):
+//   a      = A[row lane&15][k lane>>4]
+//   b      = B[k lane>>4][col lane&15]
+//   acc[v] = C[row 4v + (lane>>4)][col lane&15]
+// so after the K loop a lane holds all 13 sums of its four (sky, column)
+// points and the 4x4 factorisation + solve run in its own registers.
+//
+// Blocking: one workgroup (4 waves) owns ONE 16-column tile for the
+// whole sky.  The operand with reuse is the product tile (read once per
+// sky tile, 48x at nsky = 768), so it is staged ONCE per block into LDS
+// as Bs[5][Kp][16] — a wave's b read is 4 rows x 16 contiguous doubles,
+// conflict-free.  Wave w walks sky tiles w, w+4, ...; its a operands
+// come straight from the (L2-resident, < 1 MB) antenna table and the
+// three coefficient products are formed in registers: a 64-sky round of
+// coefficient planes would need 5 x Kp x 64 doubles of LDS (174 KB at
+// P = 67) next to the resident product tile, and no two lanes of a
+// block share a coefficient value anyway.
+//
+// fe_skymax keeps the running sky maximum per lane, reduces the four
+// row groups by shuffles and the four waves through 16 LDS slots: a
+// column is owned by exactly one block, there are no atomics, and the
+// result is bitwise reproducible.  Ties go to the lowest sky index.
+
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+#define MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+
+#define FE_WAVES 4
+#define FE_THREADS (FE_WAVES * 64)
+#define FE_RCOND 1e-12
+
+// the 13 (coefficient, product) sums of one point
+enum {
+  S_P2SS = 0, S_P2SC, S_P2CC,  // F+^2  x ss, sc, cc
+  S_PXSS, S_PXSC, S_PXCC,      // F+Fx  x ss, sc, cc
+  S_X2SS, S_X2SC, S_X2CC,      // Fx^2  x ss, sc, cc
+  S_PSR, S_PCR,                // F+    x sr, cr
+  S_XSR, S_XCR,                // Fx    x sr, cr
+  FE_NSUM
+};
+
+static __device__ __forceinline__ bool fe_pivot_ok(double s, double mjj) {
+  // false for s <= rcond * M_jj, NaN and +-inf
+  return (s > FE_RCOND * mjj) && (s < INFINITY);
+}
+
+// Fe of one point from its 13 sums: LDL^T of the 4x4 M (the pivots d_j
+// are the squared Cholesky diagonal, so the degeneracy test is the
+// Cholesky pivot test), unit-lower forward solve z = L^-1 N, and
+// Fe = 1/2 sum_j z_j^2 / d_j = 1/2 y^T y with y the Cholesky solve.
+// Returns false (point skipped) on a degenerate or non-finite pivot.
+static __device__ __forceinline__ bool fe_point(const double* s, double* fe) {
+  // filters: 0 = F+ sin, 1 = F+ cos, 2 = Fx sin, 3 = Fx cos
+  const double m00 = s[S_P2SS], m01 = s[S_P2SC], m02 = s[S_PXSS];
+  const double m03 = s[S_PXSC], m11 = s[S_P2CC], m12 = s[S_PXSC];
+  const double m13 = s[S_PXCC], m22 = s[S_X2SS], m23 = s[S_X2SC];
+  const double m33 = s[S_X2CC];
+
+  const double d0 = m00;
+  if (!fe_pivot_ok(d0, m00)) return false;
+  const double i0 = 1.0 / d0;
+  const double l10 = m01 * i0, l20 = m02 * i0, l30 = m03 * i0;
+
+  const double d1 = fma(-l10, m01, m11);
+  if (!fe_pivot_ok(d1, m11)) return false;
+  const double i1 = 1.0 / d1;
+  const double t21 = fma(-l20, m01, m12);
+  const double t31 = fma(-l30, m01, m13);
+  const double l21 = t21 * i1, l31 = t31 * i1;
+
+  const double d2 = fma(-l21, t21, fma(-l20, m02, m22));
+  if (!fe_pivot_ok(d2, m22)) return false;
+  const double i2 = 1.0 / d2;
+  const double t32 = fma(-l31, t21, fma(-l30, m02, m23));
+  const double l32 = t32 * i2;
+
+  const double d3 = fma(-l32, t32, fma(-l31, t31, fma(-l30, m03, m33)));
+  if (!fe_pivot_ok(d3, m33)) return false;
+  const double i3 = 1.0 / d3;
+
+  const double z0 = s[S_PSR];
+  const double z1 = fma(-l10, z0, s[S_PCR]);
+  const double z2 = fma(-l21, z1, fma(-l20, z0, s[S_XSR]));
+  const double z3 = fma(-l32, z2, fma(-l31, z1, fma(-l30, z0, s[S_XCR])));
+  *fe = 0.5 * fma(z3 * z3, i3, fma(z2 * z2, i2, fma(z1 * z1, i1, z0 * z0 * i0)));
+  return true;
+}
+
+// grid = ceil(D*F / 16) column tiles;  block = 256 (4 waves)
+// dynamic LDS = 5 * Kp * 16 doubles (Kp = P rounded up to 4)
+// SKYMAX = false: fe (D, nsky, F), NaN at skipped points
+// SKYMAX = true : femax/argmax/nskip (D, F)
+// Occupancy target 3 waves/SIMD: 13 accumulator quads are 104 VGPRs, so
+// 4 waves/SIMD (128) cannot hold them; at 3 the compiler keeps them in
+// VGPRs (150 total, no AGPR copies, no scratch) and three blocks' product
+// tiles (43.5 KB each at P = 67) fit the 160 KB LDS.
+template <bool SKYMAX>
+__global__ __launch_bounds__(FE_THREADS, 3) void fe_sky_kernel(
+    const double* __restrict__ prods /*(P, D, 5, F)*/,
+    const double* __restrict__ ant /*(nsky, P, 2)*/, int P, int D, int F,
+    int nsky, double* __restrict__ fe /*(D, nsky, F)*/,
+    double* __restrict__ femax /*(D, F)*/, int* __restrict__ argmax /*(D, F)*/,
+    int* __restrict__ nskip /*(D, F)*/) {
+  extern __shared__ double Bs[];  // [5][Kp][16]
+  __shared__ double red_v[FE_WAVES][16];
+  __shared__ int red_i[FE_WAVES][16];
+  __shared__ int red_n[FE_WAVES][16];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+  const int li = lane & 15;  // a row (sky) / b,acc column
+  const int lk = lane >> 4;  // k index / acc row group
+  const int Kp = (P + 3) & ~3;
+  const int nks = Kp >> 2;
+  const long NC = (long)D * F;
+  const long n0 = (long)blockIdx.x * 16;
+
+  // stage the product tile: Bs[c][k][j] = prods[k][d][c][f] of column
+  // n0 + j, zero for k >= P and for columns past D*F.  j is the fastest
+  // thread index, so the loads are contiguous in f.
+  {
+    const int j = tid & 15;
+    const long n = n0 + j;
+    const bool cok = n < NC;
+    const long d = cok ? n / F : 0;
+    const long f = cok ? n % F : 0;
+    const long cbase = d * 5 * F + f;
+    for (int r = tid >> 4; r < 5 * Kp; r += FE_THREADS / 16) {
+      const int k = r / 5;
+      const int c = r - 5 * k;
+      double v = 0.0;
+      if (cok && k < P) v = prods[(long)k * D * 5 * F + cbase + (long)c * F];
+      Bs[((long)c * Kp + k) * 16 + j] = v;
+    }
+  }
+  __syncthreads();
+
+  const long ncol = n0 + li;  // this lane's column
+  const bool colok = ncol < NC;
+  const long cd = colok ? ncol / F : 0;
+  const long cf = colok ? ncol % F : 0;
+
+  double best = -INFINITY;
+  int besti = -1;
+  int nsk = 0;
+
+  const int nst = (nsky + 15) >> 4;
+  for (int st = wv; st < nst; st += FE_WAVES) {
+    const int s0 = st << 4;
+    const int arow = s0 + li;  // the sky row this lane feeds as a
+    const bool aok = arow < nsky;
+    const double* ap = ant + (long)(aok ? arow : 0) * P * 2;
+
+    f64x4 acc[FE_NSUM];
+#pragma unroll
+    for (int i = 0; i < FE_NSUM; ++i) acc[i] = f64x4{0, 0, 0, 0};
+
+    // software-prefetched antenna pair of the next k-step
+    double fp = 0.0, fx = 0.0;
+    if (aok && lk < P) {
+      fp = ap[2 * lk];
+      fx = ap[2 * lk + 1];
+    }
+    for (int ks = 0; ks < nks; ++ks) {
+      const int k = 4 * ks + lk;
+      double nfp = 0.0, nfx = 0.0;
+      if (aok && k + 4 < P) {
+        nfp = ap[2 * (k + 4)];
+        nfx = ap[2 * (k + 4) + 1];
+      }
+      const double p2 = fp * fp, px = fp * fx, x2 = fx * fx;
+      const double bss = Bs[((long)0 * Kp + k) * 16 + li];
+      const double bcc = Bs[((long)1 * Kp + k) * 16 + li];
+      const double bsc = Bs[((long)2 * Kp + k) * 16 + li];
+      const double bsr = Bs[((long)3 * Kp + k) * 16 + li];
+      const double bcr = Bs[((long)4 * Kp + k) * 16 + li];
+      acc[S_P2SS] = MFMA_F64(p2, bss, acc[S_P2SS]);
+      acc[S_P2SC] = MFMA_F64(p2, bsc, acc[S_P2SC]);
+      acc[S_P2CC] = MFMA_F64(p2, bcc, acc[S_P2CC]);
+      acc[S_PXSS] = MFMA_F64(px, bss, acc[S_PXSS]);
+      acc[S_PXSC] = MFMA_F64(px, bsc, acc[S_PXSC]);
+      acc[S_PXCC] = MFMA_F64(px, bcc, acc[S_PXCC]);
+      acc[S_X2SS] = MFMA_F64(x2, bss, acc[S_X2SS]);
+      acc[S_X2SC] = MFMA_F64(x2, bsc, acc[S_X2SC]);
+      acc[S_X2CC] = MFMA_F64(x2, bcc, acc[S_X2CC]);
+      acc[S_PSR] = MFMA_F64(fp, bsr, acc[S_PSR]);
+      acc[S_PCR] = MFMA_F64(fp, bcr, acc[S_PCR]);
+      acc[S_XSR] = MFMA_F64(fx, bsr, acc[S_XSR]);
+      acc[S_XCR] = MFMA_F64(fx, bcr, acc[S_XCR]);
+      fp = nfp;
+      fx = nfx;
+    }
+
+    // per-lane epilogue: the four (sky 4v + lk, column li) points
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int sky = s0 + 4 * v + lk;
+      if (!colok || sky >= nsky) continue;
+      double s[FE_NSUM];
+#pragma unroll
+      for (int i = 0; i < FE_NSUM; ++i) s[i] = acc[i][v];
+      double val = 0.0;
+      const bool ok = fe_point(s, &val) && (fabs(val) < INFINITY);
+      if constexpr (SKYMAX) {
+        if (!ok) {
+          ++nsk;
+        } else if (val > best) {  // sky ascends per lane: first max stays
+          best = val;
+          besti = sky;
+        }
+      } else {
+        fe[(cd * nsky + sky) * F + cf] = ok ? val : NAN;
+      }
+    }
+  }
+
+  if constexpr (SKYMAX) {
+    // row groups lk = 0..3 share the column: lanes +16, +32
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const double ov = __shfl_xor(best, off, 64);
+      const int oi = __shfl_xor(besti, off, 64);
+      nsk += __shfl_xor(nsk, off, 64);
+      if (ov > best || (ov == best && oi >= 0 && (besti < 0 || oi < besti))) {
+        best = ov;
+        besti = oi;
+      }
+    }
+    if (lk == 0) {
+      red_v[wv][li] = best;
+      red_i[wv][li] = besti;
+      red_n[wv][li] = nsk;
+    }
+    __syncthreads();
+    if (wv == 0 && lk == 0 && colok) {
+#pragma unroll
+      for (int w = 1; w < FE_WAVES; ++w) {
+        const double ov = red_v[w][li];
+        const int oi = red_i[w][li];
+        nsk += red_n[w][li];
+        if (ov > best || (ov == best && oi >= 0 && (besti < 0 || oi < besti))) {
+          best = ov;
+          besti = oi;
+        }
+      }
+      femax[ncol] = best;
+      argmax[ncol] = besti;
+      nskip[ncol] = nsk;
+    }
+  }
+}
+
+extern "C" {
+
+// Largest P the resident product tile supports: 5 * Kp * 16 doubles of
+// dynamic LDS next to the static reduction slots, within 160 KiB.
+int fe_max_pulsars() { return 248; }
+
+static hipError_t fe_launch_common(bool skymax, const double* prods,
+                                   const double* ant, int P, int D, int F,
+                                   int nsky, double* fe, double* femax,
+                                   int* argmax, int* nskip,
+                                   hipStream_t stream) {
+  const int Kp = (P + 3) & ~3;
+  const size_t lds = (size_t)5 * Kp * 16 * sizeof(double);
+  const long ntiles = ((long)D * F + 15) / 16;
+  if (ntiles == 0 || nsky == 0) return hipSuccess;
+  const void* fn = skymax ? (const void*)fe_sky_kernel<true>
+                          : (const void*)fe_sky_kernel<false>;
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(
+        fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  const dim3 grid((unsigned)ntiles), blk(FE_THREADS);
+  if (skymax)
+    hipLaunchKernelGGL(fe_sky_kernel<true>, grid, blk, lds, stream, prods,
+                       ant, P, D, F, nsky, fe, femax, argmax, nskip);
+  else
+    hipLaunchKernelGGL(fe_sky_kernel<false>, grid, blk, lds, stream, prods,
+                       ant, P, D, F, nsky, fe, femax, argmax, nskip);
+  return hipGetLastError();
+}
+
+int launch_fe_assemble(const double* prods, const double* ant, int P, int D,
+                       int F, int nsky, double* fe, hipStream_t stream) {
+  return (int)fe_launch_common(false, prods, ant, P, D, F, nsky, fe, nullptr,
+                               nullptr, nullptr, stream);
+}
+
+int launch_fe_skymax(const double* prods, const double* ant, int P, int D,
+                     int F, int nsky, double* femax, int* argmax, int* nskip,
+                     hipStream_t stream) {
+  return (int)fe_launch_common(true, prods, ant, P, D, F, nsky, nullptr,
+                               femax, argmax, nskip, stream);
+}
+
+}  // extern "C"

@@ -21,6 +21,7 @@ ext = CUDAExtension(
     sources=[
         "fastfp_amd/ops/hip/bindings.cpp",
         "fastfp_amd/ops/hip/fastfp_kernels.hip",
+        "fastfp_amd/ops/hip/fe_kernels.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

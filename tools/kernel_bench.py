@@ -2,6 +2,11 @@
 
 Usage (GPU box): python tools/kernel_bench.py
 Prints per-kernel wall time and fp64 TFLOP/s at the NMFp bench shape.
+
+    python tools/kernel_bench.py fe [P D F nsky m]
+
+times the Fe-on-device kernels (trsm_prods, fe_assemble, fe_skymax);
+defaults P=67, D=256, F=200, nsky=768, m=120.
 """
 
 import sys
@@ -85,5 +90,60 @@ def main():
         print(f"sbgemm F={Fs:6d} ks={ks}: {t*1e6:9.1f} us  {flops/t/1e12:6.2f} TF/s")
 
 
+def main_fe(P=67, D=256, F=200, nsky=768, m=120):
+    """Fe on device: products mode of the solve + the two sky kernels.
+
+    Synthetic but well-posed inputs: the timed solve runs on a real
+    batched Cholesky factor; the sky kernels run on positive-definite
+    per-pulsar 2x2 product blocks so every 4x4 M is non-degenerate
+    (nskip is checked to be zero — a skipped point would shorten the
+    epilogue)."""
+    mp = (m + 15) // 16 * 16
+    ntoa = 2000
+    rng = np.random.default_rng(0)
+    T = torch.as_tensor(rng.normal(size=(P, ntoa, m)), dtype=torch.float64,
+                        device=DEV)
+    TNT = (T.transpose(1, 2) @ T * 1e12).contiguous()  # (P, m, m)
+    del T
+    phiinv = torch.as_tensor(rng.uniform(0.5, 2.0, (P, D, m)) * 1e10,
+                             dtype=torch.float64, device=DEV)
+    RHS = torch.zeros((P, mp, 2 * F + 1), dtype=torch.float64, device=DEV)
+    sNs = torch.ones((P, 3, F), dtype=torch.float64, device=DEV) * 1e13
+    sNr = torch.ones((P, 2, F), dtype=torch.float64, device=DEV)
+    L, invd = ext.chol_batch(TNT, phiinv, mp)
+    out = torch.empty((P, D, 5, F), dtype=torch.float64, device=DEV)
+    t = timeit(lambda: ext.trsm_prods(L, invd, RHS, sNs, sNr, out, 1.0),
+               iters=30, warmup=3)
+    flops = P * D * (mp * mp / 2) * (2 * F + 2) * 2
+    print(f"trsm_prods  P={P} D={D} F={F} mp={mp}: {t*1e3:9.3f} ms"
+          f"  {flops/t/1e12:6.2f} TF/s")
+    del L, invd, out, TNT, phiinv
+
+    prods = np.empty((P, D, 5, F))
+    prods[:, :, 0] = rng.uniform(1.0, 2.0, (P, D, F))
+    prods[:, :, 1] = rng.uniform(1.0, 2.0, (P, D, F))
+    prods[:, :, 2] = 0.1 * rng.normal(size=(P, D, F))
+    prods[:, :, 3:] = rng.normal(size=(P, D, 2, F))
+    prods = torch.as_tensor(prods, device=DEV)
+    ant = torch.as_tensor(rng.normal(size=(nsky, P, 2)), device=DEV)
+    points = float(nsky) * D * F
+    flops = points * 13 * 2 * P  # the pulsar sums; the 4x4 solve is extra
+    t = timeit(lambda: ext.fe_assemble(prods, ant), iters=50, warmup=5)
+    print(f"fe_assemble nsky={nsky}: {t*1e3:9.3f} ms  {flops/t/1e12:6.2f} TF/s"
+          f"  ({points*8/t/1e9:7.1f} GB/s map write)")
+    t = timeit(lambda: ext.fe_skymax(prods, ant), iters=50, warmup=5)
+    print(f"fe_skymax   nsky={nsky}: {t*1e3:9.3f} ms  {flops/t/1e12:6.2f} TF/s"
+          f"  ({flops:.3g} flops = 13*2*P per point)")
+    femax, argmax, nskip = ext.fe_skymax(prods, ant)
+    fmap = ext.fe_assemble(prods, ant)
+    assert int(nskip.sum()) == 0, "bench inputs must be non-degenerate"
+    assert torch.equal(femax, fmap.max(dim=1).values)
+    print(f"check: nskip=0, skymax == max(map) bitwise; "
+          f"femax range [{float(femax.min()):.3g}, {float(femax.max()):.3g}]")
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "fe":
+        main_fe(*[int(a) for a in sys.argv[2:]])
+    else:
+        main()
