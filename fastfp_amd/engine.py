@@ -36,9 +36,12 @@ from __future__ import annotations
 import contextlib
 import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
+
+from fastfp_amd import ops
 
 
 @contextlib.contextmanager
@@ -59,6 +62,62 @@ def _t64(x, device):
     if isinstance(x, torch.Tensor):
         return x.to(device=device, dtype=torch.float64)
     return torch.as_tensor(np.asarray(x, dtype=np.float64), device=device)
+
+
+class SolveSystem(NamedTuple):
+    """One per-draw solve as the kernels take it: Cholesky of
+    ``A + diag(d)``, forward solve of ``RHS``, and the per-frequency
+    2x2 closure ``M = S - gsign * W.W``, ``N = R - gsign * W.wu``.
+
+    direct:      ``(TNT, RHS, sNs, sNr, +1)``, ``d = phiinv``
+    compressed:  ``(G, K, M0, N0, -1)``,
+                 ``d = 1 / (phiinv[var] - delta0)``  (docs/DESIGN.md)
+
+    The same description serves one pulsar (``A`` (m, m), ``var`` a
+    slice) and the pulsar stack (``A`` (P, m, m), ``var`` one slice per
+    pulsar)."""
+
+    A: torch.Tensor
+    RHS: torch.Tensor
+    S: torch.Tensor
+    R: torch.Tensor
+    gsign: float
+    var: object = slice(None)  # columns of phiinv the diagonal is built from
+    delta0: torch.Tensor = None  # compressed only: the reference prior
+
+    def diag(self, pinv):
+        """phiinv rows (..., D, m), already cut to ``var``, -> the
+        diagonal added to ``A``."""
+        if self.delta0 is None:
+            return pinv
+        return 1.0 / (pinv - self.delta0[..., None, :])
+
+
+def _close_2x2(prods, fp_out):
+    """fp_out += 1/2 N^T M^-1 N from the five products (closed form)."""
+    M11, M22, M12, N1, N2 = prods
+    det = M11 * M22 - M12 * M12
+    fp_out += 0.5 * (N1 * N1 * M22 - 2.0 * N1 * N2 * M12 + N2 * N2 * M11) / det
+
+
+def _eager_products(system: SolveSystem, sigma):
+    """Eager Cholesky + TRSM of the (D, m, m) ``sigma``, reduced to the
+    five (D, F) products [ss, cc, sc, sr, cr] of ``system``."""
+    D, m = sigma.shape[0], sigma.shape[-1]
+    L = torch.linalg.cholesky(sigma)  # (D, m, m)
+    W = torch.linalg.solve_triangular(
+        L, system.RHS[:m, :][None].expand(D, -1, -1), upper=False
+    )  # (D, m, 2F+1)
+    wu = W[:, :, -1]  # (D, m)
+    Ws, Wc = W[:, :, 0:-1:2], W[:, :, 1:-1:2]  # (D, m, F)
+    g, S, R = system.gsign, system.S, system.R
+    return (
+        S[0][None] - g * (Ws * Ws).sum(1),
+        S[1][None] - g * (Wc * Wc).sum(1),
+        S[2][None] - g * (Ws * Wc).sum(1),
+        R[0][None] - g * torch.einsum("dmf,dm->df", Ws, wu),
+        R[1][None] - g * torch.einsum("dmf,dm->df", Wc, wu),
+    )
 
 
 class PulsarBlock:
@@ -103,8 +162,9 @@ class PulsarBlock:
         self.RHS = None  # (m, 2F+1): interleaved [s_f, c_f] columns + TNr
         self.sNs = None  # (3, F): ss, cc, sc
         self.sNr = None  # (2, F): s.r, c.r
+        self.direct = None  # SolveSystem(TNT, RHS, sNs, sNr, +1)
         # filled by enable_draw_compression (docs/DESIGN.md):
-        self.comp = None  # dict(G, K, M0, N0, var)
+        self.comp = None  # SolveSystem(G, K, M0, N0, -1, var, delta0)
 
 
 class FpEngine:
@@ -126,11 +186,14 @@ class FpEngine:
         ]
         self.freqs = None
         self._use_hip = False
+        self._ext = None  # the HIP extension module, HIP engines only
         self._side_stream = None
+        self._direct_stack = None  # stacked SolveSystems, None = not formed
+        self._comp_stack = None
+        self._pipe_bufs = None
         if self.device.type == "cuda" and not force_eager:
-            from fastfp_amd import ops
-
             ops.require_hip()  # fail loudly if the extension is missing
+            self._ext = ops._try_load()
             self._use_hip = True
             # second stream: per-pulsar chol->trsm chains are independent,
             # so alternating pulsars across two streams overlaps each
@@ -156,6 +219,7 @@ class FpEngine:
                     self._precompute_hip(blk, freqs)
                 else:
                     self._precompute_eager(blk, freqs, freq_chunk)
+                blk.direct = SolveSystem(blk.TNT, blk.RHS, blk.sNs, blk.sNr, 1.0)
         self._stack_direct()
         return self
 
@@ -190,8 +254,6 @@ class FpEngine:
         blk.RHS, blk.sNs, blk.sNr = RHS, sNs, sNr
 
     def _precompute_hip(self, blk: PulsarBlock, freqs):
-        from fastfp_amd import ops
-
         if blk.block_noise is None:
             # no freq_chunk: the HIP kernels generate the S panel in
             # LDS and need no chunking (ops.freq_precompute docstring)
@@ -311,18 +373,17 @@ class FpEngine:
             S0inv = torch.cholesky_inverse(L0)
             G = S0inv[sl, sl]
             if self._use_hip:
-                from fastfp_amd import ops
-
                 mvp = ops.check_m(mv)
                 Kp = torch.zeros((mvp, K.shape[1]), dtype=torch.float64)
                 Kp[:mv] = K
                 K = Kp
-            blk.comp = dict(
-                G=G.to(self.device).contiguous(),
-                K=K.to(self.device).contiguous(),
-                M0=M0.to(self.device).contiguous(),
-                N0=N0.to(self.device).contiguous(),
-                var=sl, mv=mv,
+            blk.comp = SolveSystem(
+                G.to(self.device).contiguous(),
+                K.to(self.device).contiguous(),
+                M0.to(self.device).contiguous(),
+                N0.to(self.device).contiguous(),
+                -1.0,
+                var=sl,
                 delta0=delta0.to(self.device),
             )
         self._probe_compression(phiinv_fixed)
@@ -344,53 +405,27 @@ class FpEngine:
             if blk.comp is None:
                 continue
             pinv = _t64(pf, self.device).reshape(1, -1)
-            c = blk.comp
+            ref = blk.direct
+            if self._use_hip and blk.m > 128:
+                # above m=128 the GPU direct factor routes through
+                # rocSOLVER; for the probe's REFERENCE arm prefer
+                # the CPU LAPACK eager path on this one draw
+                # (compression precompute is already pinned to CPU,
+                # so this adds one more small host round trip at
+                # setup time only)
+                ref = SolveSystem(*(t.cpu() for t in ref[:4]), ref.gsign)
             fpA = torch.zeros((1, F), dtype=torch.float64, device=self.device)
-            fpB = torch.zeros_like(fpA)
-            phi_var = (1.0 / (pinv[:, c["var"]] - c["delta0"][None, :])).contiguous()
+            fpB = torch.zeros((1, F), dtype=torch.float64, device=ref.A.device)
             try:
-                if self._use_hip and blk.m > 128:
-                    # above m=128 the GPU direct factor routes through
-                    # rocSOLVER; for the probe's REFERENCE arm prefer
-                    # the CPU LAPACK eager path on this one draw
-                    # (compression precompute is already pinned to CPU,
-                    # so this adds one more small host round trip at
-                    # setup time only)
-                    from fastfp_amd import ops
-
-                    ops.chol_trsm_fp_accum(
-                        c["G"], phi_var, c["K"], c["M0"], c["N0"], fpA,
-                        gsign=-1.0,
+                for system, out in ((blk.comp, fpA), (ref, fpB)):
+                    p = pinv.to(out.device)
+                    self._accumulate(
+                        system, system.diag(p[:, system.var]).contiguous(), out
                     )
-                    pinv_c = pinv.cpu()
-                    sigma_c = blk.TNT.cpu()[None, :, :] + torch.diag_embed(pinv_c)
-                    fpB_c = torch.zeros((1, F), dtype=torch.float64)
-                    self._accum_eager_mats(
-                        sigma_c, blk.RHS[: blk.m].cpu(), blk.sNs.cpu(),
-                        blk.sNr.cpu(), fpB_c, 1.0,
-                    )
-                    fpB = fpB_c.to(self.device)
-                elif self._use_hip:
-                    from fastfp_amd import ops
-
-                    ops.chol_trsm_fp_accum(
-                        c["G"], phi_var, c["K"], c["M0"], c["N0"], fpA,
-                        gsign=-1.0,
-                    )
-                    ops.chol_trsm_fp_accum(
-                        blk.TNT, pinv.contiguous(), blk.RHS, blk.sNs,
-                        blk.sNr, fpB, gsign=1.0,
-                    )
-                else:
-                    sigc = c["G"][None, :, :] + torch.diag_embed(phi_var)
-                    self._accum_eager_mats(
-                        sigc, c["K"], c["M0"], c["N0"], fpA, -1.0
-                    )
-                    sigma = blk.TNT[None, :, :] + torch.diag_embed(pinv)
-                    self._accum_eager(blk, sigma, fpB)
             except torch.linalg.LinAlgError:
                 blk.comp = None  # pathological probe (e.g. phi < jitter)
                 continue
+            fpB = fpB.to(self.device)
             # error against the SPECTRUM scale: per-frequency relative
             # error is meaningless at cancellation-dominated frequencies
             # (docs/DESIGN.md §8) and mis-flags healthy models
@@ -402,50 +437,83 @@ class FpEngine:
             if not bool(torch.isfinite(err)) or float(err) > tol:
                 blk.comp = None
 
-    def _stack_direct(self):
-        """Stack per-pulsar TNT/RHS/sNs/sNr for single-launch DIRECT
-        sweeps (same dimensions across pulsars; used by the plain-Fp
-        phiinv path and the compression-margin fallback)."""
-        self._direct_stack = None
-        if not self._use_hip:
-            return
-        ms = {blk.m for blk in self.blocks}
-        rs = {tuple(blk.RHS.shape) for blk in self.blocks if blk.RHS is not None}
-        if len(ms) != 1 or len(rs) != 1 or self.blocks[0].m > 256:
-            return
-        self._direct_stack = dict(
-            TNT=torch.stack([b.TNT for b in self.blocks]).contiguous(),
-            RHS=torch.stack([b.RHS for b in self.blocks]).contiguous(),
-            sNs=torch.stack([b.sNs for b in self.blocks]).contiguous(),
-            sNr=torch.stack([b.sNr for b in self.blocks]).contiguous(),
+    def _stack(self, systems):
+        """Stack per-pulsar systems of one shape into a single
+        ``(P, ...)`` system, so a whole sweep is ONE chol launch + ONE
+        trsm launch per draw chunk (grid.z = pulsar) — no per-pulsar
+        launch gaps or tail quantization.  Per-pulsar Fp planes are
+        summed deterministically by torch.  None when the stack does
+        not form (eager engine, a missing system, ragged shapes, or a
+        dimension beyond the solve kernels)."""
+        if not self._use_hip or any(s is None for s in systems):
+            return None
+        shapes = {(tuple(s.A.shape), tuple(s.RHS.shape)) for s in systems}
+        if len(shapes) != 1 or systems[0].A.shape[-1] > ops.MAX_MP:
+            return None
+        A, RHS, S, R = (
+            torch.stack(ts).contiguous()
+            for ts in zip(*(s[:4] for s in systems))
         )
+        delta0 = None
+        if systems[0].delta0 is not None:
+            delta0 = torch.stack([s.delta0 for s in systems]).contiguous()
+        return SolveSystem(A, RHS, S, R, systems[0].gsign,
+                           var=[s.var for s in systems], delta0=delta0)
+
+    def _stack_direct(self):
+        """Stacked DIRECT system (same dimensions across pulsars; used
+        by the plain-Fp phiinv path, the compression-margin fallback
+        and the Fe products)."""
+        self._direct_stack = self._stack([blk.direct for blk in self.blocks])
 
     def _stack_compression(self):
-        """When every pulsar compresses to the same variable dimension,
-        stack the per-pulsar G/K/M0/N0 so the whole sweep is ONE chol
-        launch + ONE trsm launch per draw chunk (grid.z = pulsar) — no
-        per-pulsar launch gaps or tail quantization.  Per-pulsar Fp
-        planes are summed deterministically by torch."""
-        self._comp_stack = None
-        if not self._use_hip:
-            return
-        comps = [blk.comp for blk in self.blocks]
-        if any(c is None for c in comps):
-            return
-        mvs = {c["G"].shape[0] for c in comps}
-        kshapes = {tuple(c["K"].shape) for c in comps}
-        if len(mvs) != 1 or len(kshapes) != 1:
-            return
-        vars_ = [c["var"] for c in comps]
-        self._comp_stack = dict(
-            G=torch.stack([c["G"] for c in comps]).contiguous(),
-            K=torch.stack([c["K"] for c in comps]).contiguous(),
-            M0=torch.stack([c["M0"] for c in comps]).contiguous(),
-            N0=torch.stack([c["N0"] for c in comps]).contiguous(),
-            delta0=torch.stack([c["delta0"] for c in comps]).contiguous(),
-            vars=vars_,
-            mv=comps[0]["G"].shape[0],
-        )
+        """Stacked COMPRESSED system: forms when every pulsar
+        compresses to the same variable dimension."""
+        self._comp_stack = self._stack([blk.comp for blk in self.blocks])
+
+    def _rows(self, phiinvs):
+        """Per-pulsar phiinvs, each (m,) or (D, m) -> (list of (D, m)
+        device tensors, whether the input was draw-batched)."""
+        rows = [_t64(p, self.device) for p in phiinvs]
+        batched = rows[0].dim() == 2
+        return [p[None, :] if p.dim() == 1 else p for p in rows], batched
+
+    def compression_margin_per_draw(self, phiinvs) -> torch.Tensor:
+        """Per-draw compression margin: (D,) tensor of
+        min over pulsars/bins of phiinv_d / delta0.  Basis of the
+        per-draw hybrid split (NMFp.sweep): draws above the guard run
+        compressed, the (rare) prior-corner draws run the exact direct
+        path — one extreme draw no longer forces a whole batch off the
+        fast path.  Returns +inf per draw when nothing is compressed.
+
+        No device sync: per-pulsar mins are stacked and reduced on
+        device.  When every pulsar compresses with the same variable
+        slice (the stacked homogeneous case), the whole check is one
+        stack, one divide and one min."""
+        st = self._comp_stack
+        if (
+            st is not None
+            and all(sl == st.var[0] for sl in st.var)
+            and all(
+                isinstance(p, torch.Tensor)
+                and p.device == self.device
+                and p.dim() == 2
+                for p in phiinvs
+            )
+        ):
+            pall = torch.stack(list(phiinvs))  # (P, D, m)
+            ratio = pall[:, :, st.var[0]] / st.delta0[:, None, :]
+            return ratio.amin(dim=(0, 2))
+        rows, _ = self._rows(phiinvs)
+        mins = [
+            (p[:, blk.comp.var] / blk.comp.delta0[None, :]).min(dim=1).values
+            for blk, p in zip(self.blocks, rows)
+            if blk.comp is not None
+        ]
+        if not mins:
+            return torch.full((rows[0].shape[0],), float("inf"),
+                              dtype=torch.float64, device=self.device)
+        return torch.stack(mins).min(dim=0).values
 
     def compression_margin(self, phiinvs) -> float:
         """min over pulsars/draws/bins of phiinv_d / delta_0.  The
@@ -455,60 +523,9 @@ class FpEngine:
         the NaN cliff — measured 2e-10 error at margin 1.7).  Callers
         fall back to the exact direct path below 1.5.
 
-        One device sync total: per-pulsar mins are stacked and reduced
-        on device (a per-pulsar ``float()`` cost 67 syncs per draw
-        batch in the CLI hot loop).  When every pulsar compresses with
-        the same variable slice (the stacked homogeneous case), the
-        whole check is ~4 kernels."""
-        st = getattr(self, "_comp_stack", None)
-        if (
-            st is not None
-            and all(sl == st["vars"][0] for sl in st["vars"])
-            and all(
-                isinstance(p, torch.Tensor)
-                and p.device == self.device
-                and p.dim() == 2
-                for p in phiinvs
-            )
-        ):
-            pall = torch.stack(list(phiinvs))  # (P, D, m)
-            ratio = pall[:, :, st["vars"][0]] / st["delta0"][:, None, :]
-            return float(ratio.min())
-        mins = []
-        for blk, pinv in zip(self.blocks, phiinvs):
-            if blk.comp is None:
-                continue
-            p = _t64(pinv, self.device)
-            p = p[None, :] if p.dim() == 1 else p
-            mins.append(
-                (p[:, blk.comp["var"]] / blk.comp["delta0"][None, :]).min()
-            )
-        if not mins:
-            return float("inf")
-        return float(torch.stack(mins).min())
-
-    def compression_margin_per_draw(self, phiinvs) -> torch.Tensor:
-        """Per-draw compression margin: (D,) tensor of
-        min over pulsars/bins of phiinv_d / delta0.  Basis of the
-        per-draw hybrid split (NMFp.sweep): draws above the guard run
-        compressed, the (rare) prior-corner draws run the exact direct
-        path — one extreme draw no longer forces a whole batch off the
-        fast path.  Returns +inf per draw when nothing is compressed."""
-        mins = []
-        for blk, pinv in zip(self.blocks, phiinvs):
-            if blk.comp is None:
-                continue
-            p = _t64(pinv, self.device)
-            p = p[None, :] if p.dim() == 1 else p
-            mins.append(
-                (p[:, blk.comp["var"]] / blk.comp["delta0"][None, :])
-                .min(dim=1).values
-            )
-        if not mins:
-            D = phiinvs[0].shape[0] if phiinvs[0].dim() == 2 else 1
-            return torch.full((D,), float("inf"), dtype=torch.float64,
-                              device=self.device)
-        return torch.stack(mins).min(dim=0).values
+        One device sync total (a per-pulsar ``float()`` cost 67 syncs
+        per draw batch in the CLI hot loop)."""
+        return float(self.compression_margin_per_draw(phiinvs).min())
 
     def disable_draw_compression(self):
         for blk in self.blocks:
@@ -519,6 +536,22 @@ class FpEngine:
     # ------------------------------------------------------------------
     # sweeps
     # ------------------------------------------------------------------
+    def _accumulate(self, system: SolveSystem, diag, fp_out, sigma=None):
+        """fp_out (D, F) += Fp of ``system`` with the (D, m) ``diag``
+        on its A: the HIP kernels on a HIP engine, eager torch (the
+        unit-test oracle path) otherwise and for host-resident systems.
+        ``sigma``: a caller-supplied dense A + diag(d) for the eager
+        path (the ``get_mats_fp`` contract)."""
+        if self._use_hip and diag.is_cuda:
+            ops.chol_trsm_fp_accum(
+                system.A, diag, system.RHS, system.S, system.R, fp_out,
+                gsign=system.gsign,
+            )
+            return
+        if sigma is None:
+            sigma = system.A[None, :, :] + torch.diag_embed(diag)
+        _close_2x2(_eager_products(system, sigma), fp_out)
+
     def sweep(
         self,
         phiinvs=None,
@@ -540,10 +573,10 @@ class FpEngine:
         """
         assert self.freqs is not None, "call precompute(freqs) first"
         F = self.freqs.shape[0]
+        rows = None
         if phiinvs is not None:
-            first = _t64(phiinvs[0], self.device)
-            batched = first.dim() == 2
-            D = first.shape[0] if batched else 1
+            rows, batched = self._rows(phiinvs)
+            D = rows[0].shape[0]
         else:
             first = _t64(sigmas[0], self.device)
             batched = first.dim() == 3
@@ -553,19 +586,16 @@ class FpEngine:
         if fp is None:
             fp = torch.zeros((D, F), dtype=torch.float64, device=self.device)
 
-        stack = getattr(self, "_comp_stack", None)
-        if stack is not None and phiinvs is not None and not force_direct:
-            return self._sweep_stacked(phiinvs, fp, D, F, draw_chunk, batched)
-        dstack = getattr(self, "_direct_stack", None)
-        if (
-            dstack is not None
-            and phiinvs is not None
-            and (force_direct
-                 or all(blk.comp is None for blk in self.blocks))
+        stack = None
+        if rows is not None and not force_direct:
+            stack = self._comp_stack
+        if stack is None and rows is not None and (
+            force_direct or all(blk.comp is None for blk in self.blocks)
         ):
-            return self._sweep_stacked_direct(
-                phiinvs, fp, D, F, draw_chunk, batched
-            )
+            stack = self._direct_stack
+        if stack is not None:
+            self._sweep_stacked(stack, rows, fp, draw_chunk)
+            return fp[0] if not batched else fp
 
         fp_side = None
         main_stream = None
@@ -586,10 +616,11 @@ class FpEngine:
                     else contextlib.nullcontext()
                 )
                 fp_tgt = (fp_side if side else fp)[lo:hi]
+                direct = force_direct or blk.comp is None
+                system = blk.direct if direct else blk.comp
                 with stream_ctx:
-                    if phiinvs is not None:
-                        pinv = _t64(phiinvs[i], self.device)
-                        pinv = pinv[None, :] if pinv.dim() == 1 else pinv[lo:hi]
+                    if rows is not None:
+                        pinv = rows[i][lo:hi]
                         sigma = None
                     else:
                         sg = _t64(sigmas[i], self.device)
@@ -599,30 +630,12 @@ class FpEngine:
                             torch.diagonal(sigma, dim1=-2, dim2=-1)
                             - torch.diagonal(blk.TNT)[None, :]
                         )
-                    if blk.comp is not None and not force_direct:
-                        # Schur-compressed: C_d = diag(1/Delta_d) + G
-                        c = blk.comp
-                        phi_var = (
-                            1.0 / (pinv[:, c["var"]] - c["delta0"][None, :])
-                        ).contiguous()
-                        if self._use_hip:
-                            from fastfp_amd import ops
-
-                            ops.chol_trsm_fp_accum(
-                                c["G"], phi_var, c["K"], c["M0"], c["N0"],
-                                fp_tgt, gsign=-1.0,
-                            )
-                        else:
-                            sigc = c["G"][None, :, :] + torch.diag_embed(phi_var)
-                            self._accum_eager_mats(
-                                sigc, c["K"], c["M0"], c["N0"], fp_tgt, -1.0
-                            )
-                    elif self._use_hip:
-                        self._accum_hip(blk, pinv.contiguous(), fp_tgt)
-                    else:
-                        if sigma is None:
-                            sigma = blk.TNT[None, :, :] + torch.diag_embed(pinv)
-                        self._accum_eager(blk, sigma, fp_tgt)
+                    self._accumulate(
+                        system,
+                        system.diag(pinv[:, system.var]).contiguous(),
+                        fp_tgt,
+                        sigma=sigma if direct else None,
+                    )
 
         if self._use_hip:
             ev2 = torch.cuda.Event()
@@ -650,7 +663,7 @@ class FpEngine:
         chunk0 = chunks[0][1] - chunks[0][0]
         nmax = P * chunk0
         key = ("pipebuf", nmax, mp)
-        bufs = getattr(self, "_pipe_bufs", None)
+        bufs = self._pipe_bufs
         if bufs is None or bufs[0] != key:
             L0 = torch.empty((nmax, mp, mp), dtype=torch.float64, device=dev)
             L1 = torch.empty_like(L0)
@@ -695,126 +708,57 @@ class FpEngine:
             ev2.record(main)
             solve_done[b] = ev2
 
-    def _sweep_stacked(self, phiinvs, fp, D, F, draw_chunk, batched):
-        """Pulsar-batched compressed sweep: one chol + one trsm launch
-        per draw chunk across ALL pulsars."""
-        from fastfp_amd import ops
-
-        st = self._comp_stack
-        P = len(self.blocks)
-        mv = st["mv"]
-        pin = []
-        for i in range(P):
-            p = _t64(phiinvs[i], self.device)
-            p = p[None, :] if p.dim() == 1 else p
-            pin.append(p[:, st["vars"][i]])
-        pinv_var = torch.stack(pin)  # (P, D, mv)
-        fp_pp = torch.empty((P, min(draw_chunk, D), F),
-                            dtype=torch.float64, device=self.device)
+    def _stacked_chunks(self, st: SolveSystem, rows, draw_chunk):
+        """Draw chunks of a stacked sweep: the ``(lo, hi)`` list and a
+        function giving a chunk's contiguous (P, hi-lo, m) diagonal.
+        The per-pulsar rows are gathered and stacked once."""
+        pinv = torch.stack([p[:, v] for p, v in zip(rows, st.var)])  # (P, D, m)
+        D = pinv.shape[1]
         chunks = [(lo, min(lo + draw_chunk, D))
                   for lo in range(0, D, draw_chunk)]
-        if self._use_hip and len(chunks) > 1:
+        return chunks, lambda lo, hi: st.diag(pinv[:, lo:hi, :]).contiguous()
+
+    def _sweep_stacked(self, st: SolveSystem, rows, fp, draw_chunk):
+        """Pulsar-batched sweep of a stacked system: one chol + one
+        trsm launch per draw chunk across ALL pulsars, accumulated into
+        ``fp`` (D, F)."""
+        ext = self._ext
+        P, F = len(rows), fp.shape[1]
+        chunks, diag = self._stacked_chunks(st, rows, draw_chunk)
+        fp_pp = torch.empty((P, chunks[0][1], F), dtype=torch.float64,
+                            device=self.device)
+        mp = ops.pad16(st.A.shape[-1])
+        if len(chunks) > 1 and mp <= ops.MAX_MP_CHOL:
             # SOFTWARE PIPELINE across draw chunks: the Cholesky is
             # latency-bound (~82% parked waves), the solve is
             # throughput-bound, so chunk k+1's factor runs on a side
             # stream UNDER chunk k's solve and its parked cycles are
-            # filled with solve work.
-            mvp = ops.pad16(st["G"].shape[-1])
-
+            # filled with solve work.  Above MAX_MP_CHOL the factor is
+            # rocSOLVER's, which does not write into caller buffers.
             def factor_into(L, invd, lo, hi):
-                from fastfp_amd.ops import _fastfp_hip as ext
-
-                phi_var = (
-                    1.0 / (pinv_var[:, lo:hi, :]
-                           - st["delta0"][:, None, :])
-                ).contiguous()
                 n = P * (hi - lo)
-                ext.chol_batch_into(st["G"], phi_var, mvp,
-                                    L[:n], invd[:n])
+                ext.chol_batch_into(st.A, diag(lo, hi), mp, L[:n], invd[:n])
 
             def solve(L, invd, lo, hi, pp):
-                from fastfp_amd.ops import _fastfp_hip as ext
-
                 n = P * (hi - lo)
-                ext.trsm_fp_accum(L[:n], invd[:n], st["K"], st["M0"],
-                                  st["N0"], pp, -1.0)
+                ext.trsm_fp_accum(L[:n], invd[:n], st.RHS, st.S, st.R, pp,
+                                  st.gsign)
 
-            self._pipeline_chunks(chunks, P, mvp, F, fp, fp_pp,
+            self._pipeline_chunks(chunks, P, mp, F, fp, fp_pp,
                                   factor_into, solve)
-            return fp[0] if not batched else fp
+            return
 
         for lo, hi in chunks:
-            phi_var = (
-                1.0 / (pinv_var[:, lo:hi, :] - st["delta0"][:, None, :])
-            ).contiguous()
+            d = diag(lo, hi)
             if hi - lo == fp_pp.shape[1]:
                 pp = fp_pp
             else:  # tail chunk: a dim-1 slice would be non-contiguous
                 pp = torch.empty((P, hi - lo, F), dtype=torch.float64,
                                  device=self.device)
             pp.zero_()
-            ops.chol_trsm_fp_accum(
-                st["G"], phi_var, st["K"], st["M0"], st["N0"], pp,
-                gsign=-1.0,
-            )
+            ops.chol_trsm_fp_accum(st.A, d, st.RHS, st.S, st.R, pp,
+                                   gsign=st.gsign)
             fp[lo:hi] += pp.sum(dim=0)
-        return fp[0] if not batched else fp
-
-    def _sweep_stacked_direct(self, phiinvs, fp, D, F, draw_chunk, batched):
-        """Pulsar-batched DIRECT sweep (no compression): one chol + one
-        trsm launch per draw chunk on the full-m system."""
-        from fastfp_amd import ops
-
-        st = self._direct_stack
-        P = len(self.blocks)
-        pin = []
-        for i in range(P):
-            p = _t64(phiinvs[i], self.device)
-            p = p[None, :] if p.dim() == 1 else p
-            pin.append(p)
-        pinv_all = torch.stack(pin)  # (P, D, m)
-        fp_pp = torch.empty((P, min(draw_chunk, D), F),
-                            dtype=torch.float64, device=self.device)
-        chunks = [(lo, min(lo + draw_chunk, D))
-                  for lo in range(0, D, draw_chunk)]
-        m = st["TNT"].shape[-1]
-        if self._use_hip and len(chunks) > 1 and ops.pad16(m) <= ops.MAX_MP_CHOL:
-            # same factor/solve software pipeline as the compressed path
-            mp = ops.pad16(m)
-
-            def factor_into(L, invd, lo, hi):
-                from fastfp_amd.ops import _fastfp_hip as ext
-
-                n = P * (hi - lo)
-                ext.chol_batch_into(
-                    st["TNT"], pinv_all[:, lo:hi, :].contiguous(), mp,
-                    L[:n], invd[:n],
-                )
-
-            def solve(L, invd, lo, hi, pp):
-                from fastfp_amd.ops import _fastfp_hip as ext
-
-                n = P * (hi - lo)
-                ext.trsm_fp_accum(L[:n], invd[:n], st["RHS"], st["sNs"],
-                                  st["sNr"], pp, 1.0)
-
-            self._pipeline_chunks(chunks, P, mp, F, fp, fp_pp,
-                                  factor_into, solve)
-            return fp[0] if not batched else fp
-
-        for lo, hi in chunks:
-            if hi - lo == fp_pp.shape[1]:
-                pp = fp_pp
-            else:
-                pp = torch.empty((P, hi - lo, F), dtype=torch.float64,
-                                 device=self.device)
-            pp.zero_()
-            ops.chol_trsm_fp_accum(
-                st["TNT"], pinv_all[:, lo:hi, :].contiguous(), st["RHS"],
-                st["sNs"], st["sNr"], pp, gsign=1.0,
-            )
-            fp[lo:hi] += pp.sum(dim=0)
-        return fp[0] if not batched else fp
 
     def sweep_products(self, sigmas=None, phiinvs=None) -> torch.Tensor:
         """Per-pulsar corrected inner products
@@ -833,35 +777,18 @@ class FpEngine:
         the engine's device (torch batched Cholesky/solve — setup-
         scale work, not the draw-batched Fp hot path)."""
         assert self.freqs is not None, "call precompute(freqs) first"
-        F = self.freqs.shape[0]
-        vals = sigmas if sigmas is not None else phiinvs
-        first = _t64(vals[0], self.device)
-        batched = first.dim() == (3 if sigmas is not None else 2)
-        D = first.shape[0] if batched else 1
-        out = torch.empty((len(self.blocks), D, 5, F),
-                          dtype=torch.float64, device=self.device)
-        for i, blk in enumerate(self.blocks):
-            if sigmas is not None:
-                sigma = _t64(sigmas[i], self.device)
-                sigma = sigma[None] if sigma.dim() == 2 else sigma
-            else:
-                pinv = _t64(phiinvs[i], self.device)
-                pinv = pinv[None, :] if pinv.dim() == 1 else pinv
-                sigma = blk.TNT[None] + torch.diag_embed(pinv)
-            m = blk.m
-            L = torch.linalg.cholesky(sigma)  # (D, m, m)
-            W = torch.linalg.solve_triangular(
-                L, blk.RHS[:m, :][None].expand(D, -1, -1), upper=False
-            )  # (D, m, 2F+1)
-            wu = W[:, :, -1]
-            Ws, Wc = W[:, :, 0:-1:2], W[:, :, 1:-1:2]
-            out[i, :, 0] = blk.sNs[0][None] - (Ws * Ws).sum(1)
-            out[i, :, 1] = blk.sNs[1][None] - (Wc * Wc).sum(1)
-            out[i, :, 2] = blk.sNs[2][None] - (Ws * Wc).sum(1)
-            out[i, :, 3] = blk.sNr[0][None] - torch.einsum(
-                "dmf,dm->df", Ws, wu)
-            out[i, :, 4] = blk.sNr[1][None] - torch.einsum(
-                "dmf,dm->df", Wc, wu)
+        if sigmas is not None:
+            dense = [_t64(s, self.device) for s in sigmas]
+            batched = dense[0].dim() == 3
+            dense = [s[None] if s.dim() == 2 else s for s in dense]
+        else:
+            rows, batched = self._rows(phiinvs)
+            dense = [blk.TNT[None] + torch.diag_embed(p)
+                     for blk, p in zip(self.blocks, rows)]
+        out = torch.stack([
+            torch.stack(_eager_products(blk.direct, sigma), dim=1)
+            for blk, sigma in zip(self.blocks, dense)
+        ])  # (P, D, 5, F)
         return out[:, 0] if not batched else out
 
     def sweep_products_hip(self, phiinvs, draw_chunk: int = 32) -> torch.Tensor:
@@ -877,67 +804,22 @@ class FpEngine:
         Otherwise (CPU/eager engine, ragged bases, larger m) it returns
         ``self.sweep_products(phiinvs=...)``."""
         assert self.freqs is not None, "call precompute(freqs) first"
-        from fastfp_amd import ops
-
-        st = getattr(self, "_direct_stack", None)
-        if st is None or ops.pad16(st["TNT"].shape[-1]) > ops.MAX_MP_CHOL:
+        st = self._direct_stack
+        if st is None or ops.pad16(st.A.shape[-1]) > ops.MAX_MP_CHOL:
             return self.sweep_products(phiinvs=phiinvs)
-        from fastfp_amd.ops import _fastfp_hip as ext
-
-        F = self.freqs.shape[0]
-        P = len(self.blocks)
-        mp = ops.pad16(st["TNT"].shape[-1])
-        pin = [_t64(p, self.device) for p in phiinvs]
-        batched = pin[0].dim() == 2
-        pinv_all = torch.stack(
-            [p if batched else p[None, :] for p in pin])  # (P, D, m)
-        D = pinv_all.shape[1]
+        ext = self._ext
+        mp = ops.pad16(st.A.shape[-1])
+        rows, batched = self._rows(phiinvs)
+        P, D, F = len(rows), rows[0].shape[0], self.freqs.shape[0]
+        chunks, diag = self._stacked_chunks(st, rows, draw_chunk)
         out = torch.empty((P, D, 5, F), dtype=torch.float64,
                           device=self.device)
-        for lo in range(0, D, draw_chunk):
-            hi = min(lo + draw_chunk, D)
-            L, invd = ext.chol_batch(
-                st["TNT"], pinv_all[:, lo:hi, :].contiguous(), mp)
-            if lo == 0 and hi == D:
-                ext.trsm_prods(L, invd, st["RHS"], st["sNs"], st["sNr"],
-                               out, 1.0)
-            else:  # a draw slice of `out` is not contiguous
-                part = torch.empty((P, hi - lo, 5, F), dtype=torch.float64,
-                                   device=self.device)
-                ext.trsm_prods(L, invd, st["RHS"], st["sNs"], st["sNr"],
-                               part, 1.0)
+        for lo, hi in chunks:
+            L, invd = ext.chol_batch(st.A, diag(lo, hi), mp)
+            # a draw slice of `out` is not contiguous
+            part = out if (lo, hi) == (0, D) else torch.empty(
+                (P, hi - lo, 5, F), dtype=torch.float64, device=self.device)
+            ext.trsm_prods(L, invd, st.RHS, st.S, st.R, part, st.gsign)
+            if part is not out:
                 out[:, lo:hi] = part
         return out if batched else out[:, 0]
-
-    def _accum_eager(self, blk: PulsarBlock, sigma, fp_out):
-        """Eager per-pulsar accumulation: Cholesky + TRSM + fused 2x2."""
-        self._accum_eager_mats(sigma, blk.RHS, blk.sNs, blk.sNr, fp_out, 1.0)
-
-    def _accum_eager_mats(self, sigma, RHS, sNs, sNr, fp_out, gsign):
-        Dc = sigma.shape[0]
-        L = torch.linalg.cholesky(sigma)  # (Dc, m, m)
-        RHSb = RHS.unsqueeze(0).expand(Dc, -1, -1)
-        W = torch.linalg.solve_triangular(L, RHSb, upper=False)
-        wu = W[:, :, -1]  # (Dc, m)
-        Ws = W[:, :, 0:-1:2]  # (Dc, m, F)
-        Wc = W[:, :, 1:-1:2]
-        g_ss = (Ws * Ws).sum(dim=1)  # (Dc, F)
-        g_cc = (Wc * Wc).sum(dim=1)
-        g_sc = (Ws * Wc).sum(dim=1)
-        n_s = torch.einsum("dmf,dm->df", Ws, wu)
-        n_c = torch.einsum("dmf,dm->df", Wc, wu)
-
-        M11 = sNs[0][None, :] - gsign * g_ss
-        M22 = sNs[1][None, :] - gsign * g_cc
-        M12 = sNs[2][None, :] - gsign * g_sc
-        N1 = sNr[0][None, :] - gsign * n_s
-        N2 = sNr[1][None, :] - gsign * n_c
-        det = M11 * M22 - M12 * M12
-        fp_out += 0.5 * (N1 * N1 * M22 - 2.0 * N1 * N2 * M12 + N2 * N2 * M11) / det
-
-    def _accum_hip(self, blk: PulsarBlock, phiinv, fp_out):
-        from fastfp_amd import ops
-
-        ops.chol_trsm_fp_accum(
-            blk.TNT, phiinv, blk.RHS, blk.sNs, blk.sNr, fp_out
-        )

@@ -77,6 +77,31 @@ def check_m(m: int) -> int:
 # ----------------------------------------------------------------------
 # op wrappers (thin; shapes documented in the kernels)
 # ----------------------------------------------------------------------
+def _basis_rhs(A, weights, toas, TNr, freqs):
+    """RHS (mp, 2F+1) = [A^T diag(weights) S | TNr] through the fused
+    signal-basis MFMA DGEMM (sbgemm), rows zero-padded to mp."""
+    ext = _try_load()
+    F = int(freqs.shape[0])
+    ntoa, m = A.shape
+    mp = pad16(m)  # sbgemm is M-tiled: no 128 cap on the basis size
+    RHS = torch.zeros((mp, 2 * F + 1), dtype=torch.float64, device=A.device)
+    F2 = 2 * F
+    ctiles = (F2 + 63) // 64
+    # split K to fill the 256-CU chip when the frequency grid is small;
+    # partial planes + a deterministic torch reduction keep fp64
+    # bitwise-reproducible (no atomics)
+    ksplit = max(1, min(8, (512 + ctiles - 1) // ctiles, (ntoa + 255) // 256))
+    if ksplit == 1:
+        ext.sbgemm(A, toas, weights, freqs, RHS, 0, 2 * F + 1, mp, 1)
+    else:
+        part = torch.empty((ksplit, mp, F2), dtype=torch.float64,
+                           device=A.device)
+        ext.sbgemm(A, toas, weights, freqs, part, mp * F2, F2, mp, ksplit)
+        RHS[:, :F2] = part.sum(dim=0)
+    RHS[:m, -1] = TNr
+    return RHS
+
+
 def freq_precompute(toas, Nvec, r, T, TNr, freqs):
     """GPU frequency precompute for one pulsar.
 
@@ -91,31 +116,11 @@ def freq_precompute(toas, Nvec, r, T, TNr, freqs):
     (F, ntoa) intermediate ever exists to bound.
     """
     ext = _try_load()
-    F = int(freqs.shape[0])
-    ntoa, m = T.shape
-    mp = pad16(m)  # sbgemm is M-tiled: no 128 cap on the basis size
-    device = T.device
     Ninv = (1.0 / Nvec).contiguous()
     Nr = (r / Nvec).contiguous()
     freqs = freqs.contiguous()
-
     sNs, sNr = ext.sigdots(toas.contiguous(), Ninv, Nr, freqs)
-
-    RHS = torch.zeros((mp, 2 * F + 1), dtype=torch.float64, device=device)
-    F2 = 2 * F
-    ctiles = (F2 + 63) // 64
-    # split K to fill the 256-CU chip when the frequency grid is small;
-    # partial planes + a deterministic torch reduction keep fp64
-    # bitwise-reproducible (no atomics)
-    ksplit = max(1, min(8, (512 + ctiles - 1) // ctiles, (ntoa + 255) // 256))
-    if ksplit == 1:
-        ext.sbgemm(T, toas, Ninv, freqs, RHS, 0, 2 * F + 1, mp, 1)
-    else:
-        part = torch.empty((ksplit, mp, F2), dtype=torch.float64, device=device)
-        ext.sbgemm(T, toas, Ninv, freqs, part, mp * F2, F2, mp, ksplit)
-        RHS[:, :F2] = part.sum(dim=0)
-    RHS[:m, -1] = TNr
-    return RHS, sNs, sNr
+    return _basis_rhs(T, Ninv, toas, TNr, freqs), sNs, sNr
 
 
 def freq_precompute_block(toas, block_noise, Nr, V, TNr, freqs):
@@ -128,31 +133,14 @@ def freq_precompute_block(toas, block_noise, Nr, V, TNr, freqs):
     per-epoch blocks are diagonal + rank-1, see fastfp_amd.blocknoise).
     """
     ext = _try_load()
-    F = int(freqs.shape[0])
-    ntoa, m = V.shape
-    mp = pad16(m)  # sbgemm is M-tiled: no 128 cap on the basis size
-    device = V.device
     freqs = freqs.contiguous()
-
-    bt = block_noise.tensors(device)
+    bt = block_noise.tensors(V.device)
     sNs, sNr = ext.sigdots_block(
         toas.contiguous(), bt["uvec"].contiguous(), Nr.contiguous(), freqs,
         bt["beta"].contiguous(), bt["offsets"], bt["sizes"],
     )
-
-    RHS = torch.zeros((mp, 2 * F + 1), dtype=torch.float64, device=device)
-    F2 = 2 * F
-    ones = torch.ones(ntoa, dtype=torch.float64, device=device)
-    ctiles = (F2 + 63) // 64
-    ksplit = max(1, min(8, (512 + ctiles - 1) // ctiles, (ntoa + 255) // 256))
-    if ksplit == 1:
-        ext.sbgemm(V, toas, ones, freqs, RHS, 0, 2 * F + 1, mp, 1)
-    else:
-        part = torch.empty((ksplit, mp, F2), dtype=torch.float64, device=device)
-        ext.sbgemm(V, toas, ones, freqs, part, mp * F2, F2, mp, ksplit)
-        RHS[:, :F2] = part.sum(dim=0)
-    RHS[:m, -1] = TNr
-    return RHS, sNs, sNr
+    ones = torch.ones(V.shape[0], dtype=torch.float64, device=V.device)
+    return _basis_rhs(V, ones, toas, TNr, freqs), sNs, sNr
 
 
 def chol_trsm_fp_accum(TNT, phiinv, RHS, sNs, sNr, fp_out, gsign=1.0):

@@ -84,32 +84,10 @@ void sbgemm(torch::Tensor T, torch::Tensor toas, torch::Tensor ninv,
                 (int)ksplit, stream());
 }
 
-// chol_batch: TNT (m,m) or (P,m,m), phiinv (D,m) or (P,D,m)
-// -> L (P*D,mp,mp), invd (P*D,mp/16,16,16)
-std::vector<torch::Tensor> chol_batch(torch::Tensor TNT, torch::Tensor phiinv,
-                                      int64_t mp) {
-  check_f64(TNT, "TNT");
-  check_f64(phiinv, "phiinv");
-  const bool batched = TNT.dim() == 3;
-  const int P = batched ? TNT.size(0) : 1;
-  const int m = TNT.size(batched ? 1 : 0);
-  const int D = phiinv.size(batched ? 1 : 0);
-  TORCH_CHECK(phiinv.dim() == (batched ? 3 : 2), "phiinv rank");
-  TORCH_CHECK(phiinv.size(batched ? 2 : 1) == m, "phiinv width != m");
-  TORCH_CHECK(mp % 16 == 0 && mp <= 128 && mp >= m,
-              "chol_batch requires m <= 128 (solve dimension); got m=", m);
-  auto opts = TNT.options();
-  auto L = torch::empty({(long)P * D, mp, mp}, opts);
-  auto invd = torch::empty({(long)P * D, mp / 16, 16, 16}, opts);
-  launch_chol_batch(TNT.data_ptr<double>(), phiinv.data_ptr<double>(), m,
-                    (int)mp, D, P, L.data_ptr<double>(),
-                    invd.data_ptr<double>(), stream());
-  return {L, invd};
-}
-
-// chol_batch_into: same as chol_batch but writing into caller-owned
-// L/invd (the engine's ping-pong pipeline buffers — avoids per-chunk
-// allocator churn across streams).
+// chol_batch_into: TNT (m,m) or (P,m,m), phiinv (D,m) or (P,D,m) ->
+// caller-owned L (P*D,mp,mp), invd (P*D,mp/16,16,16) (the engine's
+// ping-pong pipeline buffers — avoids per-chunk allocator churn across
+// streams).
 void chol_batch_into(torch::Tensor TNT, torch::Tensor phiinv, int64_t mp,
                      torch::Tensor L, torch::Tensor invd) {
   check_f64(TNT, "TNT");
@@ -132,33 +110,79 @@ void chol_batch_into(torch::Tensor TNT, torch::Tensor phiinv, int64_t mp,
                     invd.data_ptr<double>(), stream());
 }
 
-// trsm_fp_accum: single pulsar (L (D,mp,mp), RHS (mp,2F+1), sNs (3,F),
-// fp (D,F)) or pulsar-batched (L (P*D,mp,mp), RHS (P,mp,2F+1),
-// sNs (P,3,F), fp (P,D,F)); accumulates in place.
-void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
-                   torch::Tensor sNs, torch::Tensor sNr, torch::Tensor fp,
-                   double gsign) {
+// chol_batch: allocate L/invd and factor into them.
+std::vector<torch::Tensor> chol_batch(torch::Tensor TNT, torch::Tensor phiinv,
+                                      int64_t mp) {
+  const bool batched = TNT.dim() == 3;
+  const int m = TNT.size(batched ? 1 : 0);
+  TORCH_CHECK(phiinv.dim() == (batched ? 3 : 2), "phiinv rank");
+  TORCH_CHECK(mp % 16 == 0 && mp <= 128 && mp >= m,
+              "chol_batch requires m <= 128 (solve dimension); got m=", m);
+  const long n = (batched ? TNT.size(0) : 1) * phiinv.size(batched ? 1 : 0);
+  auto L = torch::empty({n, mp, mp}, TNT.options());
+  auto invd = torch::empty({n, mp / 16, 16, 16}, TNT.options());
+  chol_batch_into(TNT, phiinv, mp, L, invd);
+  return {L, invd};
+}
+
+namespace {
+
+struct SolveDims {
+  int P, mp, F, D;
+};
+
+// Shapes of one solve, shared by trsm_fp_accum and trsm_prods: single
+// pulsar (L (D,mp,mp), RHS (mp,2F+1), sNs (3,F), sNr (2,F)) or
+// pulsar-batched (L (P*D,mp,mp), RHS (P,mp,2F+1), sNs (P,3,F),
+// sNr (P,2,F)).  `out` is (D,[K,]F) / (P,D,[K,]F); K = 0 means no such
+// dimension.
+SolveDims check_solve(const torch::Tensor& L, const torch::Tensor& invd,
+                      const torch::Tensor& RHS, const torch::Tensor& sNs,
+                      const torch::Tensor& sNr, const torch::Tensor& out,
+                      const char* oname, int K) {
   check_f64(L, "L");
   check_f64(invd, "invd");
   check_f64(RHS, "RHS");
   check_f64(sNs, "sNs");
   check_f64(sNr, "sNr");
-  check_f64(fp, "fp");
+  check_f64(out, oname);
   const bool batched = RHS.dim() == 3;
-  const int P = batched ? RHS.size(0) : 1;
-  const int mp = L.size(1);
-  const int F = sNs.size(batched ? 2 : 1);
-  const int D = fp.size(batched ? 1 : 0);
-  TORCH_CHECK(L.size(0) == (long)P * D, "L batch != P*D");
-  TORCH_CHECK(RHS.size(batched ? 1 : 0) == mp &&
-                  RHS.size(batched ? 2 : 1) == 2 * F + 1,
+  const int b = batched ? 1 : 0;
+  SolveDims d;
+  d.P = batched ? RHS.size(0) : 1;
+  d.mp = L.size(1);
+  d.F = sNs.size(b + 1);
+  TORCH_CHECK(out.dim() == b + (K ? 3 : 2), oname, " rank");
+  d.D = out.size(b);
+  TORCH_CHECK(L.dim() == 3 && L.size(2) == d.mp &&
+                  L.size(0) == (long)d.P * d.D,
+              "L batch != P*D");
+  TORCH_CHECK(invd.numel() == (long)d.P * d.D * d.mp * 16, "invd shape");
+  TORCH_CHECK(RHS.size(b) == d.mp && RHS.size(b + 1) == 2 * d.F + 1,
               "RHS shape");
-  TORCH_CHECK(fp.dim() == (batched ? 3 : 2) && fp.size(batched ? 2 : 1) == F,
-              "fp shape");
-  TORCH_CHECK(mp % 16 == 0 && mp <= 256, "mp must be <=256, multiple of 16");
+  TORCH_CHECK(sNs.numel() == (long)d.P * 3 * d.F &&
+                  sNr.numel() == (long)d.P * 2 * d.F,
+              "sNs/sNr shape");
+  TORCH_CHECK((!batched || out.size(0) == d.P) &&
+                  (!K || out.size(b + 1) == K) &&
+                  out.size(out.dim() - 1) == d.F,
+              oname, " shape");
+  return d;
+}
+
+}  // namespace
+
+// trsm_fp_accum: solve + fused 2x2 reduction, accumulating in place
+// into fp (D,F) / (P,D,F).
+void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
+                   torch::Tensor sNs, torch::Tensor sNr, torch::Tensor fp,
+                   double gsign) {
+  const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, fp, "fp", 0);
+  TORCH_CHECK(d.mp % 16 == 0 && d.mp <= 256,
+              "mp must be <=256, multiple of 16");
   launch_trsm_fp(L.data_ptr<double>(), invd.data_ptr<double>(),
                  RHS.data_ptr<double>(), sNs.data_ptr<double>(),
-                 sNr.data_ptr<double>(), mp, F, D, P, gsign,
+                 sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
                  fp.data_ptr<double>(), stream());
 }
 
@@ -169,38 +193,15 @@ void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
 void trsm_prods(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                 torch::Tensor sNs, torch::Tensor sNr, torch::Tensor out,
                 double gsign) {
-  check_f64(L, "L");
-  check_f64(invd, "invd");
-  check_f64(RHS, "RHS");
-  check_f64(sNs, "sNs");
-  check_f64(sNr, "sNr");
-  check_f64(out, "out");
-  const bool batched = RHS.dim() == 3;
-  const int P = batched ? RHS.size(0) : 1;
-  const int mp = L.size(1);
-  const int F = sNs.size(batched ? 2 : 1);
-  TORCH_CHECK(out.dim() == (batched ? 4 : 3), "out rank");
-  const int D = out.size(batched ? 1 : 0);
-  TORCH_CHECK(L.dim() == 3 && L.size(2) == mp && L.size(0) == (long)P * D,
-              "L batch != P*D");
-  TORCH_CHECK(invd.numel() == (long)P * D * mp * 16, "invd shape");
-  TORCH_CHECK(RHS.size(batched ? 1 : 0) == mp &&
-                  RHS.size(batched ? 2 : 1) == 2 * F + 1,
-              "RHS shape");
-  TORCH_CHECK(sNs.numel() == (long)P * 3 * F && sNr.numel() == (long)P * 2 * F,
-              "sNs/sNr shape");
-  TORCH_CHECK((!batched || out.size(0) == P) &&
-                  out.size(batched ? 2 : 1) == 5 &&
-                  out.size(batched ? 3 : 2) == F,
-              "out shape");
-  TORCH_CHECK(mp % 16 == 0 && mp >= 16 && mp <= 128,
+  const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, out, "out", 5);
+  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 128,
               "trsm_prods supports a padded solve dimension mp <= 128 "
-              "(multiple of 16); got mp=", mp,
+              "(multiple of 16); got mp=", d.mp,
               " — use FpEngine.sweep_products for larger bases");
-  if (D == 0 || F == 0) return;
+  if (d.D == 0 || d.F == 0) return;
   launch_trsm_prods(L.data_ptr<double>(), invd.data_ptr<double>(),
                     RHS.data_ptr<double>(), sNs.data_ptr<double>(),
-                    sNr.data_ptr<double>(), mp, F, D, P, gsign,
+                    sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
                     out.data_ptr<double>(), stream());
 }
 

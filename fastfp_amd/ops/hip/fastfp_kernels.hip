@@ -24,21 +24,34 @@
 //                        W = L^-1 [B | TNr] fused with the per-frequency
 //                        2x2 Gram/solve/Fp reduction; W lives entirely
 //                        in LDS and never touches HBM (subsumes
-//                        utils.py:54 + fastfp.py:81-90)
+//                        utils.py:54 + fastfp.py:81-90); its products
+//                        mode stores the five corrected products
+//                        instead of Fp (the Fe input).  mp <= 128
+//   trsm_fp_rl_kernel  — right-looking form of the same solve, the
+//                        path for 128 < mp <= 256
+//   diag_inv_kernel    — inverted 16x16 diagonal blocks of a rocSOLVER
+//                        factor (the mp > 128 direct path)
+//   sigdots_block_kernel — sigdots for block-diagonal N
+//
+// Each launcher below is one dispatch: there are no environment-
+// selected variants.  The alternatives that were tried and measured
+// neutral or slower (LDS-resident and wave-level solves, a
+// double-buffered sbgemm, other grid orders) are recorded in
+// docs/TUNING_NOTES.md.
 //
 // Conventions:
 //   wave = 64 lanes (CDNA);  MFMA v_mfma_f64_16x16x4f64:
 //     A[i][k]: lane l holds A[i = l&15][k = l>>4]
 //     B[k][j]: lane l holds B[k = l>>4][j = l&15]
 //     D/C    : lane l holds rows 4*v + (l>>4) (v=0..3), col l&15 (probed: tools/mfma_probe.hip)
-//   mp = m padded to a multiple of 16, mp <= 128.  Pad rows of Sigma
+//   mp = m padded to a multiple of 16, mp <= 128 for the LDS-resident
+//   Cholesky and mp <= 256 for the solve.  Pad rows of Sigma
 //   are identity (L pad = I) and pad rows of RHS are zero, so padding
 //   never changes results.
 //   All reductions have fixed order -> bitwise-deterministic fp64.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdlib.h>
 
 #define FASTFP_MAXMP 128
 #define NB 16  // Cholesky/TRSM block size (one MFMA tile)
@@ -204,103 +217,6 @@ extern "C" __global__ __launch_bounds__(512) void sbgemm_kernel(
 }
 
 // ---------------------------------------------------------------------
-// sbgemm_db: DOUBLE-BUFFERED variant of sbgemm — the next K-tile's T
-// panel + generated trig panel are staged while the current tile's
-// MFMAs run, so there is ONE barrier per K-tile instead of two and
-// the global loads + the ~100-cycle fp64 sincos hide under the MFMA
-// phase.  LDS doubles to ~50 KB (still 2+ workgroups/CU at the
-// 112-VGPR occupancy).  A/B arm: FASTFP_SBGEMM_ALGO=db.
-// ---------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(512) void sbgemm_db_kernel(
-    const double* __restrict__ T /*(ntoa, m) row-major*/,
-    const double* __restrict__ toas, const double* __restrict__ ninv,
-    const double* __restrict__ freqs, int ntoa, int m, int mp, int F2,
-    double* __restrict__ out, long plane_stride, long ldo) {
-  __shared__ double lT[2][16][FASTFP_MAXMP + 1];
-  __shared__ double lS[2][64][17];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = tid >> 6;
-  const int c0 = blockIdx.x * 64;
-  const int mbase = blockIdx.z * FASTFP_MAXMP;
-  const int mp_loc = min(FASTFP_MAXMP, mp - mbase);
-  const int jw = (wv & 3) * 16;
-  const int rh = wv >> 2;
-  const int rowbase = rh * 64;
-  const int nrt_tot = mp_loc >> 4;
-  const int rt_lo = min(rh * 4, nrt_tot);
-  const int rt_hi = min(rt_lo + 4, nrt_tot);
-
-  const int ks = gridDim.y;
-  const int kchunk = (ntoa + ks - 1) / ks;
-  const int kbeg = blockIdx.y * kchunk;
-  const int kend = min(ntoa, kbeg + kchunk);
-  double* outp = out + (long)blockIdx.y * plane_stride;
-
-  f64x4 acc[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) acc[q] = f64x4{0, 0, 0, 0};
-
-  // staging of K-tile k0 into buffer b
-#define SB_STAGE(k0, b)                                                    \
-  {                                                                        \
-    for (int idx = tid; idx < 16 * mp_loc; idx += 512) {                   \
-      const int k = idx / mp_loc, j = idx % mp_loc;                        \
-      const int gk = (k0) + k;                                             \
-      const int gj = mbase + j;                                            \
-      lT[b][k][j] = (gk < kend && gj < m) ? T[(long)gk * m + gj] : 0.0;    \
-    }                                                                      \
-    for (int idx = tid; idx < 32 * 16; idx += 512) {                       \
-      const int p = idx / 16, k = idx % 16;                                \
-      const int gk = (k0) + k;                                             \
-      const int ceven = c0 + 2 * p;                                        \
-      double sv = 0.0, cv = 0.0;                                           \
-      if (gk < kend && ceven < F2) {                                       \
-        const double wf = 2.0 * M_PI * freqs[ceven >> 1];                  \
-        sincos(wf * toas[gk], &sv, &cv);                                   \
-        const double ni = ninv[gk];                                        \
-        sv *= ni; cv *= ni;                                                \
-      }                                                                    \
-      lS[b][2 * p][k] = sv;                                                \
-      lS[b][2 * p + 1][k] = cv;                                            \
-    }                                                                      \
-  }
-
-  SB_STAGE(kbeg, 0);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = kbeg; k0 < kend; k0 += 16) {
-    if (k0 + 16 < kend) SB_STAGE(k0 + 16, buf ^ 1);
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const double b = lS[buf][jw + (lane & 15)][kk * 4 + (lane >> 4)];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        if (rt_lo + q >= rt_hi) break;
-        const double a =
-            lT[buf][kk * 4 + (lane >> 4)][rowbase + q * 16 + (lane & 15)];
-        acc[q] = MFMA_F64(a, b, acc[q]);
-      }
-    }
-    buf ^= 1;
-    __syncthreads();
-  }
-#undef SB_STAGE
-
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    if (rt_lo + q >= rt_hi) break;
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int row = mbase + rowbase + q * 16 + 4 * v + (lane >> 4);
-      const int col = c0 + jw + (lane & 15);
-      if (col < F2) outp[(long)row * ldo + col] = acc[q][v];
-    }
-  }
-}
-
-// ---------------------------------------------------------------------
 // chol_batch: per draw d, assemble Sigma = TNT + diag(phiinv[d]) (+
 // identity padding to mp) in LDS, factor L L^T = Sigma (right-looking,
 // NB=16 blocks, MFMA trailing updates), invert each 16x16 diagonal
@@ -315,22 +231,22 @@ extern "C" __global__ __launch_bounds__(512) void sbgemm_db_kernel(
 // — but the extra address arithmetic measured +16 VGPR, dropping a
 // waves/SIMD tier: net zero.  Padded layout kept.)
 //
-// TRI (FASTFP_CHOL_TRI=1, NBT <= 4): LOWER-TRIANGLE-packed Sigma —
-// row i holds i+1 entries (+1 pad), halving LDS (33.3 -> 17.4 KB at
-// mp=64) so ~7 workgroups fit per CU instead of 4; concurrency is the
-// suspected chol bottleneck (82% parked waves resist every other
-// explanation tested).  All factor-phase accesses are at-or-below the
-// diagonal; the diagonal tile's upper half is read through the
-// symmetric mirror AS_, and trailing stores into diagonal tiles are
-// lower-guarded.
-#define A_(i, j)                                                        \
-  Ash[TRI ? ((i) * ((i) + 3) / 2 + (j)) : ((i) * (NBT * 16 + 1) + (j))]
+// Sigma is LOWER-TRIANGLE-packed — row i holds i+1 entries (+1 pad),
+// halving LDS against a square layout (33.3 -> 17.4 KB at mp=64) so ~7
+// workgroups fit per CU instead of 4, and at mp=128 two instead of one
+// (the square layout is 132 KB); concurrency is the suspected chol
+// bottleneck (82% parked waves resist every other explanation tested)
+// and packing measured -13% on chol at the bench shape.  All
+// factor-phase accesses are at-or-below the diagonal; the diagonal
+// tile's upper half is read through the symmetric mirror AS_, and
+// trailing stores into diagonal tiles are lower-guarded.
+#define A_(i, j) Ash[(i) * ((i) + 3) / 2 + (j)]
 #define AS_(i, j) ((j) <= (i) ? A_(i, j) : A_(j, i))
 
 // (Forcing a 6-waves/SIMD allocation target on the small shapes got
 // there only by spilling 44 B/lane and measured neutral — reverted;
-// the no-spill allocation already reaches 5 waves with TRI.)
-template <int NBT, bool TRI = false>
+// the no-spill allocation already reaches 5 waves.)
+template <int NBT>
 __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     const double* __restrict__ TNT_all /*(P,m,m)*/,
     const double* __restrict__ phiinv_all /*(P,D,m)*/, int m, int D,
@@ -347,7 +263,7 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
   // serial diagonal phases then overlap ACROSS workgroups -- the PMC
   // profile showed 84% of wave cycles parked, profiles/).
   constexpr int mp = NBT * 16;
-  __shared__ double Ash[TRI ? mp * (mp + 3) / 2 : mp * (mp + 1)];
+  __shared__ double Ash[mp * (mp + 3) / 2];
   __shared__ double inv16[2][16][17];
 
   const int d = blockIdx.x;
@@ -359,10 +275,10 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
 
   const int nthr = blockDim.x;
   const int nwv = nthr >> 6;
-  // assemble Sigma in LDS (lower triangle only under TRI)
+  // assemble Sigma in LDS (lower triangle only)
   for (int idx = tid; idx < mp * mp; idx += nthr) {
     const int i = idx / mp, j = idx % mp;
-    if (TRI && j > i) continue;
+    if (j > i) continue;
     double v = (i < m && j < m) ? TNT[(long)i * m + j] : 0.0;
     if (i == j) v += (i < m) ? phiinv[(long)d * m + i] : 1.0;
     A_(i, j) = v;
@@ -450,7 +366,7 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
       const int i0 = ib * NB;
       f64x4 uacc;
       // diagonal tile (i0 == j1): upper half read via the symmetric
-      // mirror under TRI, and its stores lower-guarded
+      // mirror, and its stores lower-guarded
 #pragma unroll
       for (int v = 0; v < 4; ++v)
         uacc[v] = AS_(i0 + 4 * v + (lane >> 4), j1 + (lane & 15));
@@ -462,7 +378,7 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
       }
 #pragma unroll
       for (int v = 0; v < 4; ++v)
-        if (!TRI || i0 + 4 * v + (lane >> 4) >= j1 + (lane & 15))
+        if (i0 + 4 * v + (lane >> 4) >= j1 + (lane & 15))
           A_(i0 + 4 * v + (lane >> 4), j1 + (lane & 15)) = uacc[v];
     }
     __syncthreads();
@@ -494,83 +410,18 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
         }
 #pragma unroll
         for (int v = 0; v < 4; ++v)
-          if (!TRI || i0 + 4 * v + (lane >> 4) >= j0 + (lane & 15))
+          if (i0 + 4 * v + (lane >> 4) >= j0 + (lane & 15))
             A_(i0 + 4 * v + (lane >> 4), j0 + (lane & 15)) = uacc[v];
       }
     }
     __syncthreads();
   }
 
-  // write back L (full rows; upper-triangle junk is never read — TRI
-  // writes deterministic zeros there)
+  // write back L (full rows; the upper triangle is never read and
+  // gets deterministic zeros)
   for (int idx = tid; idx < mp * mp; idx += nthr) {
     const int i = idx / mp, j = idx % mp;
-    L[((long)d * mp + i) * mp + j] = (TRI && j > i) ? 0.0 : A_(i, j);
-  }
-}
-
-// ---------------------------------------------------------------------
-// chol_wave: fully IN-WAVE Cholesky for mp <= 64 — one DRAW per wave,
-// rows as lanes, the whole factor in registers with width-64 __shfl
-// broadcasts.  No LDS, no barriers, no cross-wave dependencies: every
-// wave is busy on its own draw, attacking the blocked kernel's
-// 82%-parked-waves structure at its root.  The diagonal-block
-// inverses come from the separate diag_inv kernel.  The t/j loops are
-// fully unrolled so every a[] index is compile-time (runtime indices
-// demote the register array to scratch).
-//
-// MEASURED NEGATIVE (kept as the record): 4.90 ms vs the blocked
-// kernel's 3.04 ms at the bench shape.  The ~2,080 serial-ish __shfl
-// broadcasts per draw (DS-pipe) plus 209 VGPR -> 2 waves/SIMD swamp
-// the parking win; the blocked kernel's MFMA trailing updates do the
-// same O(mp^3) work in far fewer issue slots.  Numerics validated
-// (7 GPU tests green under FASTFP_CHOL_ALGO=wave).
-// grid = (ceil(D/4), P), block = 256 (4 waves).  A/B arm only.
-// ---------------------------------------------------------------------
-template <int MP>
-__global__ __launch_bounds__(256) void chol_wave_kernel(
-    const double* __restrict__ TNT_all /*(P,m,m)*/,
-    const double* __restrict__ phiinv_all /*(P,D,m)*/, int m, int D,
-    double* __restrict__ L_all /*(P*D,mp,mp)*/) {
-  const int pp = blockIdx.y;
-  const int d = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (d >= D) return;
-  const int i = threadIdx.x & 63;  // row owned by this lane
-  const double* TNT = TNT_all + (long)pp * m * m;
-  const double* phiinv = phiinv_all + ((long)pp * D + d) * m;
-  double* L = L_all + ((long)pp * D + d) * MP * MP;
-
-  // row i of Sigma (lower triangle only; padding rows are identity)
-  double a[MP];
-#pragma unroll
-  for (int j = 0; j < MP; ++j) {
-    double v = 0.0;
-    if (i < m && j < m && j <= i) v = TNT[(long)i * m + j];
-    if (j == i) v += (i < m) ? phiinv[i] : 1.0;
-    a[j] = (i < MP) ? v : 0.0;
-  }
-
-  // unblocked right-looking factor, rows-as-lanes
-#pragma unroll
-  for (int t = 0; t < MP; ++t) {
-    const double att = __shfl(a[t], t, 64);
-    const double rdv = 1.0 / sqrt(att);
-    if (i == t)
-      a[t] = att * rdv;  // = sqrt(att)
-    else if (i > t)
-      a[t] *= rdv;
-#pragma unroll
-    for (int j = t + 1; j < MP; ++j) {
-      const double ljt = __shfl(a[t], j, 64);
-      if (i >= j) a[j] = fma(-a[t], ljt, a[j]);
-    }
-  }
-
-  // write row i (upper half as deterministic zeros)
-  if (i < MP) {
-#pragma unroll
-    for (int j = 0; j < MP; ++j)
-      L[(long)i * MP + j] = (j <= i) ? a[j] : 0.0;
+    L[((long)d * mp + i) * mp + j] = (j > i) ? 0.0 : A_(i, j);
   }
 }
 
@@ -602,17 +453,12 @@ __global__ __launch_bounds__(256) void chol_wave_kernel(
 #define FPT_FREQS 63
 #define NBMAX (FASTFP_MAXMP / 16)
 
-// SWAP: launch with grid (D, ftiles, P) instead of (ftiles, D, P) so
-// consecutive workgroups share one RHS column strip (L2-resident
-// across ~D consecutive blocks) instead of streaming 16 different
-// strips — A/B arm for the measured 2.9 ms RHS-load attribution
-// (FASTFP_TRSM_GRID=d).
 // PRODS: products mode for the sky-coherent Fe statistic — the
 // epilogue stores the five corrected products [M11, M22, M12, N1, N2]
 // = [s|s, c|c, s|c, s|r, c|r] un-collapsed into
 // out[((p*D + d)*5 + i)*F + f] (plain stores, no accumulation) instead
 // of reducing them to Fp.
-template <int NBT, int DPG, bool SWAP = false, bool PRODS = false>
+template <int NBT, int DPG, bool PRODS = false>
 __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
     const double* __restrict__ L_all /*(P*D,mp,mp)*/,
     const double* __restrict__ invd_all /*(P*D, mp/16, 16, 16)*/,
@@ -630,9 +476,13 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
   // compile-time: with a runtime index the register array is demoted to
   // scratch (288 B/lane measured) and every MFMA b-operand becomes a
   // memory load -- the whole point of the register-resident design.
-  // DPG (1 or 2) = draws per workgroup: at the compressed path's small
-  // NBT the solve is short, so two draws share the Lp/Iv staging and
-  // barriers, and their MFMA chains interleave on the pipe.
+  // DPG = draws per workgroup.  Only DPG=1 is instantiated: measured,
+  // its 8 waves/SIMD at 61 VGPR beat DPG=2 (two draws sharing the Lp/Iv
+  // staging and barriers, 4 waves/SIMD) by ~5%.  The body stays
+  // written for a general DPG: with the draw count made a constant
+  // (the ndr edge clamp below is a run-time value) the compiler emits
+  // different instructions and register counts at every NBT, and the
+  // code as generated today is the one that was measured.
   constexpr int mp = NBT * 16;
   __shared__ double Lp[2][DPG][16][NBT * 16 + 1];  // double-buffered
   __shared__ double Iv[DPG][NBT][16][17];
@@ -645,8 +495,8 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
   const double* sNs = sNs_all + (long)pp * 3 * F;
   const double* sNr = sNr_all + (long)pp * 2 * F;
   double* fp = fp_all + (long)pp * D * F;
-  const int d0 = (SWAP ? blockIdx.x : blockIdx.y) * DPG;
-  const int f0 = (SWAP ? blockIdx.y : blockIdx.x) * FPT_FREQS;
+  const int d0 = blockIdx.y * DPG;
+  const int f0 = blockIdx.x * FPT_FREQS;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wv = tid >> 6;
@@ -834,7 +684,10 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
 // independent accumulators, so the pipe can fill while the critical
 // solve chain waits.  L is staged as COLUMN panels (double-buffered,
 // row stride 19: conflict-free for the a-fragment access pattern
-// 19*li + 4*kk + lk mod 32 banks).  Selected by FASTFP_TRSM_ALGO=rl.
+// 19*li + 4*kk + lk mod 32 banks).  Measured within +-2% of the
+// left-looking kernel at NBT <= 8, so it is dispatched only for
+// NBT 9..16 (128 < mp <= 256), where the left-looking kernel's extra
+// accumulator chains would not fit the register budget.
 // ---------------------------------------------------------------------
 template <int NBT>
 __global__ __launch_bounds__(512, 4) void trsm_fp_rl_kernel(
@@ -932,168 +785,6 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_rl_kernel(
       }
     }
     __syncthreads();
-  }
-
-  // fused register/shfl reduction — identical to trsm_fp_kernel
-  if (wv == 7) {
-#pragma unroll
-    for (int rt = 0; rt < NBT; ++rt)
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-        if (li == 14) Wu[rt * 16 + 4 * v + lk] = W[rt][v];
-  }
-  __syncthreads();
-
-  // lane-split accumulation (see trsm_fp_kernel): 3 fma chains, odd
-  // halves fetched by shfl_xor after the row-group reduction
-  double a1 = 0, a2 = 0, a3 = 0;
-#pragma unroll
-  for (int rt = 0; rt < NBT; ++rt) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const double w = W[rt][v];
-      const double wp = __shfl_xor(w, 1, 64);
-      const double wu = Wu[rt * 16 + 4 * v + lk];
-      a1 = fma(w, w, a1);
-      a2 = fma(w, wu, a2);
-      a3 = fma(w, wp, a3);
-    }
-  }
-  a1 += __shfl_down(a1, 32, 64); a1 += __shfl_down(a1, 16, 64);
-  a2 += __shfl_down(a2, 32, 64); a2 += __shfl_down(a2, 16, 64);
-  a3 += __shfl_down(a3, 32, 64); a3 += __shfl_down(a3, 16, 64);
-  const double b1 = __shfl_xor(a1, 1, 64);
-  const double b2 = __shfl_xor(a2, 1, 64);
-  const int q = (jw + li) >> 1;
-  if (lk == 0 && (li & 1) == 0 && q < FPT_FREQS && f0 + q < F) {
-    const int f = f0 + q;
-    const double M11 = sNs[f] - gsign * a1;
-    const double M22 = sNs[F + f] - gsign * b1;
-    const double M12 = sNs[2 * F + f] - gsign * a3;
-    const double N1 = sNr[f] - gsign * a2;
-    const double N2 = sNr[F + f] - gsign * b2;
-    const double det = fma(M11, M22, -M12 * M12);
-    const double num =
-        fma(N1 * N1, M22, fma(-2.0 * N1, N2 * M12, N2 * N2 * M11));
-    fp[(long)d0 * F + f] += 0.5 * num / det;
-  }
-}
-
-// ---------------------------------------------------------------------
-// trsm_fp_res: fully LDS-RESIDENT variant.  The r02 PMC profile showed
-// the left-looking and right-looking kernels both stall ~40% of wave
-// cycles on the per-iteration L-panel staging barriers (waitANY 25% +
-// issue waits), NOT on the MFMA dependency chain (the RL experiment
-// measured the chain hypothesis dead: +-2%).  At the compressed shape
-// (NBT<=5) the strictly-lower triangle of L is only NBT*(NBT-1)/2
-// 16x16 tiles (12-24 KB), so the whole factor is staged ONCE at kernel
-// start and the solve loop runs with ZERO barriers and zero memory
-// waits: 2 barriers total per kernel (post-stage, pre-reduction)
-// instead of NBT+1.  Row stride 19 keeps every a-fragment read
-// bank-conflict-free (19*li + 4*kk + lk distinct mod 32).
-// Dispatched for NBT <= 5 when FASTFP_TRSM_ALGO=res (A/B arm).
-// ---------------------------------------------------------------------
-// MODE: 0 = full kernel; 1 = skip the reduction/epilogue (timing
-// attribution only — writes nothing); 2 = additionally skip the RHS
-// global loads (pure stage+solve).  Modes 1/2 exist for the phase
-// cost attribution in tools/trsm_diag.py and are never used in
-// production (FASTFP_TRSM_MODE).
-template <int NBT, int MODE = 0>
-__global__ __launch_bounds__(512, 4) void trsm_fp_res_kernel(
-    const double* __restrict__ L_all /*(P*D,mp,mp)*/,
-    const double* __restrict__ invd_all /*(P*D, mp/16, 16, 16)*/,
-    const double* __restrict__ RHS_all /*(P, mp, 2F+1)*/,
-    const double* __restrict__ sNs_all /*(P,3,F)*/,
-    const double* __restrict__ sNr_all /*(P,2,F)*/, int F, int D,
-    double gsign, double* __restrict__ fp_all /*(P,D,F)*/) {
-  constexpr int mp = NBT * 16;
-  constexpr int NTILE = NBT * (NBT - 1) / 2;  // strictly-lower tiles
-  __shared__ double Lt[NTILE > 0 ? NTILE : 1][16][19];
-  __shared__ double Iv[NBT][16][19];
-  __shared__ double Wu[NBT * 16];
-
-  const int pp = blockIdx.z;
-  const double* L = L_all + (long)pp * D * mp * mp;
-  const double* invd = invd_all + (long)pp * D * NBT * 256;
-  const double* RHS = RHS_all + (long)pp * mp * (2L * F + 1);
-  const double* sNs = sNs_all + (long)pp * 3 * F;
-  const double* sNr = sNr_all + (long)pp * 2 * F;
-  double* fp = fp_all + (long)pp * D * F;
-  const int d0 = blockIdx.y;
-  const int f0 = blockIdx.x * FPT_FREQS;
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = tid >> 6;
-  const long ldr = 2L * F + 1;
-  const int jw = wv * 16;
-  const int li = lane & 15;
-  const int lk = lane >> 4;
-
-  // stage EVERYTHING once: inverted diagonal blocks + the strictly-
-  // lower L tiles (tile t(rb,cb) = rb*(rb-1)/2 + cb)
-  for (int idx = tid; idx < NBT * 256; idx += 512)
-    Iv[idx >> 8][(idx >> 4) & 15][idx & 15] =
-        invd[(long)d0 * NBT * 256 + idx];
-  if (NTILE > 0) {
-    for (int idx = tid; idx < NTILE * 256; idx += 512) {
-      const int t = idx >> 8, r = (idx >> 4) & 15, c = idx & 15;
-      // invert t -> (rb, cb): rb = largest with rb*(rb-1)/2 <= t
-      int rb = 1;
-      while (rb * (rb + 1) / 2 <= t) ++rb;
-      const int cb = t - rb * (rb - 1) / 2;
-      Lt[t][r][c] = L[((long)d0 * mp + rb * 16 + r) * mp + cb * 16 + c];
-    }
-  }
-
-  // load RHS strip into registers (acc layout)
-  const int bc = jw + li;
-  f64x4 W[NBT];
-#pragma unroll
-  for (int rt = 0; rt < NBT; ++rt) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      double val = 1.0;
-      if (MODE < 2) {
-        const long row = rt * 16 + 4 * v + lk;
-        val = 0.0;
-        if (bc < 126) {
-          const long gc = 2L * f0 + bc;
-          if (gc < 2L * F) val = RHS[row * ldr + gc];
-        } else if (bc == 126) {
-          val = RHS[row * ldr + 2L * F];  // the u column
-        }
-      }
-      W[rt][v] = val;
-    }
-  }
-  __syncthreads();  // everything staged; solve loop is barrier-free
-
-#pragma unroll
-  for (int cb = 0; cb < NBT; ++cb) {
-    f64x4 sol = f64x4{0, 0, 0, 0};
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-      const double a = Iv[cb][li][kk * 4 + lk];
-      sol = MFMA_F64(a, W[cb][kk], sol);
-    }
-    W[cb] = sol;
-#pragma unroll
-    for (int rb = cb + 1; rb < NBT; ++rb) {
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        const double a = -Lt[rb * (rb - 1) / 2 + cb][li][kk * 4 + lk];
-        W[rb] = MFMA_F64(a, sol[kk], W[rb]);
-      }
-    }
-  }
-
-  if (MODE >= 1) {
-    // attribution mode: keep the solve live, skip reduction/epilogue
-    double s = 0.0;
-#pragma unroll
-    for (int rt = 0; rt < NBT; ++rt) s += W[rt][0];
-    if (s == 1.2345678e300) fp[0] = s;  // never true for real data
-    return;
   }
 
   // fused register/shfl reduction — identical to trsm_fp_kernel
@@ -1289,21 +980,10 @@ void launch_sbgemm(const double* T, const double* toas, const double* ninv,
                    hipStream_t stream) {
   const int ctiles = (F2 + 63) / 64;
   const int mtiles = (mp + FASTFP_MAXMP - 1) / FASTFP_MAXMP;
-  static const char* algo = getenv("FASTFP_SBGEMM_ALGO");
-  static const bool use_db = algo && 0 == __builtin_strcmp(algo, "db");
-  if (use_db) {
-    hipLaunchKernelGGL(sbgemm_db_kernel, dim3(ctiles, ksplit, mtiles),
-                       dim3(512), 0, stream, T, toas, ninv, freqs, ntoa, m,
-                       mp, F2, out, plane_stride, ldo);
-    return;
-  }
   hipLaunchKernelGGL(sbgemm_kernel, dim3(ctiles, ksplit, mtiles), dim3(512),
                      0, stream, T, toas, ninv, freqs, ntoa, m, mp, F2, out,
                      plane_stride, ldo);
 }
-
-void launch_diag_inv(const double* L, int mp, long nblk_total, double* invd,
-                     hipStream_t stream);
 
 void launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
                        int D, int P, double* L, double* invd,
@@ -1311,45 +991,10 @@ void launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
   // small matrices: 256 threads -> 4 workgroups/CU despite the 115-VGPR
   // diagonal-factor pressure; large: 512 threads for MFMA coverage
   const dim3 grid(D, P), blk(mp <= 64 ? 256 : 512);
-  // FASTFP_CHOL_ALGO=wave: fully in-wave factor (one draw per wave,
-  // no LDS/barriers) for mp <= 64; the diagonal-block inverses come
-  // from the diag_inv kernel
-  static const char* walgo = getenv("FASTFP_CHOL_ALGO");
-  static const bool use_wave = walgo && 0 == __builtin_strcmp(walgo, "wave");
-  if (use_wave && mp <= 64) {
-    const dim3 wgrid((D + 3) / 4, P);
-    switch (mp >> 4) {
-#define CHOL_WAVE_CASE(NBT) \
-      case NBT: hipLaunchKernelGGL((chol_wave_kernel<NBT * 16>), wgrid, \
-                    dim3(256), 0, stream, TNT, phiinv, m, D, L); break;
-      CHOL_WAVE_CASE(1) CHOL_WAVE_CASE(2) CHOL_WAVE_CASE(3) CHOL_WAVE_CASE(4)
-#undef CHOL_WAVE_CASE
-    }
-    launch_diag_inv(L, mp, (long)P * D * (mp >> 4), invd, stream);
-    return;
-  }
-  // Lower-triangle-packed Sigma is the DEFAULT (measured -13% on chol
-  // at the bench shape from the extra workgroup of concurrency; at
-  // mp=128 the square layout is 132 KB LDS = ONE workgroup per CU, so
-  // packing doubles concurrency).  FASTFP_CHOL_TRI=0 restores the
-  // square layout for A/B.
-  static const char* tri_env = getenv("FASTFP_CHOL_TRI");
-  static const bool tri = !(tri_env && tri_env[0] == '0');
-  if (tri) {
-    switch (mp >> 4) {
-#define CHOL_TRI_CASE(NBT) \
-      case NBT: hipLaunchKernelGGL((chol_batch_kernel<NBT, true>), grid, \
-                    blk, 0, stream, TNT, phiinv, m, D, L, invd); break;
-      CHOL_TRI_CASE(1) CHOL_TRI_CASE(2) CHOL_TRI_CASE(3) CHOL_TRI_CASE(4)
-      CHOL_TRI_CASE(5) CHOL_TRI_CASE(6) CHOL_TRI_CASE(7) CHOL_TRI_CASE(8)
-#undef CHOL_TRI_CASE
-    }
-    return;
-  }
   switch (mp >> 4) {
 #define CHOL_CASE(NBT) \
-    case NBT: hipLaunchKernelGGL(chol_batch_kernel<NBT>, grid, blk, 0, \
-                                 stream, TNT, phiinv, m, D, L, invd); break;
+    case NBT: hipLaunchKernelGGL((chol_batch_kernel<NBT>), grid, blk, \
+                  0, stream, TNT, phiinv, m, D, L, invd); break;
     CHOL_CASE(1) CHOL_CASE(2) CHOL_CASE(3) CHOL_CASE(4)
     CHOL_CASE(5) CHOL_CASE(6) CHOL_CASE(7) CHOL_CASE(8)
 #undef CHOL_CASE
@@ -1361,107 +1006,30 @@ void launch_trsm_fp(const double* L, const double* invd, const double* RHS,
                     int D, int P, double gsign, double* fp,
                     hipStream_t stream) {
   const int ftiles = (F + FPT_FREQS - 1) / FPT_FREQS;
-  const dim3 blk(512);
-  const int nb = mp >> 4;
-  // FASTFP_TRSM_ALGO selects the A/B arm: "rl" = right-looking staged
-  // panels; "res" = fully LDS-resident barrier-free (NBT <= 5, falls
-  // back to rl above that)
-  static const char* algo_env = getenv("FASTFP_TRSM_ALGO");
-  static const bool use_res = algo_env && 0 == __builtin_strcmp(algo_env, "res");
-  static const bool use_rl = algo_env && 0 == __builtin_strcmp(algo_env, "rl");
-  if (use_res && nb <= 5) {
-    const dim3 grid(ftiles, D, P);
-    // FASTFP_TRSM_MODE=1/2: phase-attribution debug arms (NBT=4 only)
-    static const char* mode_env = getenv("FASTFP_TRSM_MODE");
-    static const int mode = mode_env ? atoi(mode_env) : 0;
-    if (mode == 1 && nb == 4) {
-      hipLaunchKernelGGL((trsm_fp_res_kernel<4, 1>), grid, blk, 0, stream,
-                         L, invd, RHS, sNs, sNr, F, D, gsign, fp);
-      return;
-    }
-    if (mode == 2 && nb == 4) {
-      hipLaunchKernelGGL((trsm_fp_res_kernel<4, 2>), grid, blk, 0, stream,
-                         L, invd, RHS, sNs, sNr, F, D, gsign, fp);
-      return;
-    }
-    switch (nb) {
-#define TRSM_RES_CASE(NBT) \
-      case NBT: hipLaunchKernelGGL((trsm_fp_res_kernel<NBT>), grid, blk, 0, \
-                    stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
-      TRSM_RES_CASE(1) TRSM_RES_CASE(2) TRSM_RES_CASE(3)
-      TRSM_RES_CASE(4) TRSM_RES_CASE(5)
-#undef TRSM_RES_CASE
-    }
-    return;
-  }
-  if ((use_rl || (use_res && nb > 5)) && nb <= 8) {
-    const dim3 grid(ftiles, D, P);
-    switch (nb) {
-#define TRSM_RL_CASE(NBT) \
-      case NBT: hipLaunchKernelGGL((trsm_fp_rl_kernel<NBT>), grid, blk, 0, \
-                    stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
-      TRSM_RL_CASE(1) TRSM_RL_CASE(2) TRSM_RL_CASE(3) TRSM_RL_CASE(4)
-      TRSM_RL_CASE(5) TRSM_RL_CASE(6) TRSM_RL_CASE(7) TRSM_RL_CASE(8)
-#undef TRSM_RL_CASE
-    }
-    return;
-  }
-  // FASTFP_TRSM_GRID=d: draws-innermost grid (RHS L2-locality A/B arm)
-  static const char* grid_env = getenv("FASTFP_TRSM_GRID");
-  static const bool swap_grid = grid_env && grid_env[0] == 'd';
-  if (swap_grid && nb <= 8) {
-    const dim3 grid(D, ftiles, P);
-    switch (nb) {
-#define TRSM_SW_CASE(NBT) \
-      case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1, true>), grid, \
-                    blk, 0, stream, L, invd, RHS, sNs, sNr, F, D, gsign, \
-                    fp); break;
-      TRSM_SW_CASE(1) TRSM_SW_CASE(2) TRSM_SW_CASE(3) TRSM_SW_CASE(4)
-      TRSM_SW_CASE(5) TRSM_SW_CASE(6) TRSM_SW_CASE(7) TRSM_SW_CASE(8)
-#undef TRSM_SW_CASE
-    }
-    return;
-  }
-  // DPG selects draws per workgroup for small solves; the measured
-  // default is 1 (8 waves/SIMD at 61 VGPR beats DPG=2's 2 chains at
-  // 4 waves/SIMD by ~5%); FASTFP_TRSM_DPG=2 re-enables the A/B arm
-  static const char* dpg_env = getenv("FASTFP_TRSM_DPG");
-  static const int dpg_want = dpg_env ? atoi(dpg_env) : 1;  // measured: DPG1 (8 waves/SIMD, 61 VGPR) beats DPG2 (4 waves/SIMD) by ~5%
-  if (nb <= 4 && dpg_want >= 2) {
-    const dim3 grid(ftiles, (D + 1) / 2, P);
-    switch (nb) {
-#define TRSM_CASE2(NBT) \
-      case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 2>), grid, blk, 0, \
-                    stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
-      TRSM_CASE2(1) TRSM_CASE2(2) TRSM_CASE2(3) TRSM_CASE2(4)
-#undef TRSM_CASE2
-    }
-  } else {
-    const dim3 grid(ftiles, D, P);
-    switch (nb) {
+  const dim3 grid(ftiles, D, P), blk(512);
+  switch (mp >> 4) {
 #define TRSM_CASE(NBT) \
-      case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1>), grid, blk, 0, \
-                    stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
-      TRSM_CASE(1) TRSM_CASE(2) TRSM_CASE(3) TRSM_CASE(4)
-      TRSM_CASE(5) TRSM_CASE(6) TRSM_CASE(7) TRSM_CASE(8)
+    case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1>), grid, blk, 0, \
+                  stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
+    TRSM_CASE(1) TRSM_CASE(2) TRSM_CASE(3) TRSM_CASE(4)
+    TRSM_CASE(5) TRSM_CASE(6) TRSM_CASE(7) TRSM_CASE(8)
 #undef TRSM_CASE
-      // m > 128 (GP-ECORR direct path) dispatches the RIGHT-LOOKING
-      // variant: its single in-place accumulator set (no acc/acc2
-      // chains) keeps W = NBT*4 f64 regs per lane within budget at
-      // NBT up to 16.  The FACTOR for these sizes comes from rocSOLVER
-      // (chol_batch's LDS-resident Sigma caps at 128) + diag_inv.
+    // m > 128 (GP-ECORR direct path) dispatches the RIGHT-LOOKING
+    // variant: its single in-place accumulator set (no acc/acc2
+    // chains) keeps W = NBT*4 f64 regs per lane within budget at
+    // NBT up to 16.  The FACTOR for these sizes comes from rocSOLVER
+    // (chol_batch's LDS-resident Sigma caps at 128) + diag_inv.
 #define TRSM_BIG_CASE(NBT) \
-      case NBT: hipLaunchKernelGGL((trsm_fp_rl_kernel<NBT>), grid, blk, 0, \
-                    stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
-      TRSM_BIG_CASE(9) TRSM_BIG_CASE(10) TRSM_BIG_CASE(11) TRSM_BIG_CASE(12)
-      TRSM_BIG_CASE(13) TRSM_BIG_CASE(14) TRSM_BIG_CASE(15) TRSM_BIG_CASE(16)
+    case NBT: hipLaunchKernelGGL((trsm_fp_rl_kernel<NBT>), grid, blk, 0, \
+                  stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
+    TRSM_BIG_CASE(9) TRSM_BIG_CASE(10) TRSM_BIG_CASE(11) TRSM_BIG_CASE(12)
+    TRSM_BIG_CASE(13) TRSM_BIG_CASE(14) TRSM_BIG_CASE(15) TRSM_BIG_CASE(16)
 #undef TRSM_BIG_CASE
-    }
   }
 }
 
-// Products mode (Fe): one launch over (ftiles, D, P), mp <= 128.  No
-// A/B environment switches — there is one arm.
+
+// Products mode (Fe): one launch over (ftiles, D, P), mp <= 128.
 void launch_trsm_prods(const double* L, const double* invd, const double* RHS,
                        const double* sNs, const double* sNr, int mp, int F,
                        int D, int P, double gsign, double* out,
@@ -1471,7 +1039,7 @@ void launch_trsm_prods(const double* L, const double* invd, const double* RHS,
   const dim3 grid(ftiles, D, P);
   switch (mp >> 4) {
 #define TRSM_PRODS_CASE(NBT) \
-    case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1, false, true>), grid, \
+    case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1, true>), grid, \
                   blk, 0, stream, L, invd, RHS, sNs, sNr, F, D, gsign, out); \
       break;
     TRSM_PRODS_CASE(1) TRSM_PRODS_CASE(2) TRSM_PRODS_CASE(3)

@@ -689,3 +689,73 @@ def test_zero_residuals_give_zero_fp():
     got = FastFp(psrs).sweep(np.array([1e-8, 3e-8]), Nvecs, Ts, sigmas,
                              device="cpu")
     np.testing.assert_array_equal(got, 0.0)
+
+
+def _compressed_engine(psrs, rn_comps, gwb_comps, freqs, D, seed):
+    """CPU engine with draw compression enabled at the noise-dict
+    parameters, plus D random-draw phiinvs as (D, m) tensors."""
+    from fastfp_amd.noise import batch_phiinv
+
+    noise = {"gw_gamma": 13.0 / 3.0, "gw_log10_A": float(np.log10(2e-15))}
+    for p in psrs:
+        noise[f"{p.name}_red_noise_gamma"] = 4.0
+        noise[f"{p.name}_red_noise_log10_A"] = -14.5
+    pta = initialize_pta(psrs, noise, inc_cp=True, rn_comps=rn_comps,
+                         gwb_comps=gwb_comps)
+    TNTs, Nvecs, Ts = get_mats_nmfp(pta, noise)
+    eng = FpEngine(psrs, Nvecs, Ts, device="cpu").precompute(freqs)
+    eng.enable_draw_compression(
+        [c.var_slice for c in pta.rn_containers],
+        [c.get_phiinv(noise) for c in pta.rn_containers],
+    )
+    rng = np.random.default_rng(seed)
+    samples = {
+        n: (rng.uniform(3, 5, D) if n.endswith("gamma")
+            else rng.uniform(-15.5, -14.5, D))
+        for n in pta.params
+    }
+    piv = [p if p.dim() == 2 else p[None]
+           for p in batch_phiinv(pta.rn_containers, samples)]
+    return eng, piv
+
+
+def test_margins_agree():
+    """compression_margin is exactly the minimum of the per-draw
+    vector: all pulsars compressed, one pulsar left direct, and +inf
+    once compression is disabled."""
+    # the test_per_draw_margin_vector set-up
+    eng, piv = _compressed_engine(
+        make_synthetic_pta(npsr=2, ntoa=200, ntm=5, seed=19),
+        5, 5, np.linspace(3e-9, 5e-8, 4), D=4, seed=6)
+    assert all(blk.comp is not None for blk in eng.blocks)
+    assert eng.compression_margin(piv) == float(
+        eng.compression_margin_per_draw(piv).min())
+    # the test_mixed_compression_rank_deficient_pulsar set-up
+    eng2, piv2 = _compressed_engine(
+        make_synthetic_pta(npsr=2, ntoa=90, ntm=4, seed=23)
+        + make_synthetic_pta(npsr=1, ntoa=10, ntm=4, seed=24, ragged=False),
+        5, 4, np.linspace(4e-9, 5e-8, 6), D=4, seed=31)
+    assert [blk.comp is not None for blk in eng2.blocks] == [True, True, False]
+    assert eng2.compression_margin(piv2) == float(
+        eng2.compression_margin_per_draw(piv2).min())
+    for e, p in ((eng, piv), (eng2, piv2)):
+        assert np.isfinite(e.compression_margin(p))
+        e.disable_draw_compression()
+        assert e.compression_margin(p) == float("inf")
+        assert bool(torch.isinf(e.compression_margin_per_draw(p)).all())
+
+
+def test_sweep_products_close_to_sweep():
+    """The five products of sweep_products, closed per pulsar through
+    the 2x2 system and summed over pulsars, are the direct sweep: both
+    run the one eager W -> products reduction."""
+    eng, piv = _compressed_engine(
+        make_synthetic_pta(npsr=3, ntoa=70, ntm=3, seed=16),
+        4, 3, np.linspace(4e-9, 5e-8, 6), D=3, seed=4)
+    ss, cc, sc, sr, cr = np.moveaxis(
+        eng.sweep_products(phiinvs=piv).numpy(), 2, 0)  # each (P, D, F)
+    closed = 0.5 * (sr * sr * cc - 2.0 * sr * cr * sc + cr * cr * ss) / (
+        ss * cc - sc * sc)
+    want = eng.sweep(phiinvs=piv, force_direct=True).numpy()
+    assert want.shape == (3, 6)
+    np.testing.assert_allclose(closed.sum(axis=0), want, rtol=1e-12)

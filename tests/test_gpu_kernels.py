@@ -360,6 +360,57 @@ def test_engine_direct_stacked_gpu_matches_cpu():
     assert eng_g._direct_stack is not None, "stack should engage (same m)"
     got = eng_g.sweep(phiinvs=phiinvs).cpu().numpy()
     np.testing.assert_allclose(got, want, rtol=1e-8)
+    # draw_chunk=2 over D=5: the factor/solve pipeline with ping-pong
+    # buffers, ending in a one-draw tail chunk
+    got = eng_g.sweep(phiinvs=phiinvs, draw_chunk=2).cpu().numpy()
+    np.testing.assert_allclose(got, want, rtol=1e-8)
+
+
+def test_compressed_stacked_large_mv_multichunk_gpu():
+    """Compressed stacked sweep whose variable dimension exceeds the
+    LDS-resident Cholesky (mv = 140 > 128) over more than one draw
+    chunk: it must take the un-pipelined rocSOLVER-factored loop, not
+    the chol_batch pipeline.  Compared with the CPU engine's compressed
+    sweep of the same draws."""
+    from fastfp_amd import FpEngine, get_mats_nmfp, initialize_pta, \
+        make_synthetic_pta
+
+    psrs = make_synthetic_pta(npsr=2, ntoa=500, ntm=10, seed=51,
+                              ragged=False)
+    noise = {"gw_gamma": 13.0 / 3.0, "gw_log10_A": float(np.log10(2e-15))}
+    for p in psrs:
+        noise[f"{p.name}_red_noise_gamma"] = 4.0
+        noise[f"{p.name}_red_noise_log10_A"] = -14.5
+    # ntm 10 + 2*70 rn = 150 columns, 140 of them variable
+    pta = initialize_pta(psrs, noise, inc_cp=True, rn_comps=70,
+                         gwb_comps=10)
+    TNTs, Nvecs, Ts = get_mats_nmfp(pta, noise)
+    D = 3
+    rng = np.random.default_rng(5)
+    pars = {
+        n: (rng.uniform(2, 6, D) if n.endswith("gamma")
+            else rng.uniform(-16, -14, D))
+        for n in pta.params
+    }
+    phiinvs = [c.get_phiinv(pars).numpy() for c in pta.rn_containers]
+    freqs = np.linspace(4e-9, 6e-8, 13)
+    var_slices = [c.var_slice for c in pta.rn_containers]
+    fixed = [c.get_phiinv(noise) for c in pta.rn_containers]
+
+    results = {}
+    for dev in ("cpu", DEV):
+        eng = FpEngine(psrs, Nvecs, Ts, device=dev).precompute(freqs)
+        eng.enable_draw_compression(var_slices, fixed)
+        print(dev, "probe errors",
+              [getattr(b, "probe_err", None) for b in eng.blocks])
+        assert all(blk.comp is not None for blk in eng.blocks)
+        assert all(blk.comp.A.shape[0] == 140 for blk in eng.blocks)
+        results[dev] = eng.sweep(phiinvs=phiinvs, draw_chunk=2).cpu().numpy()
+    assert eng._comp_stack is not None
+    cpu, gpu = results["cpu"], results[DEV]
+    err = np.abs(gpu - cpu).max() / np.abs(cpu).max()
+    print("max|gpu - cpu| / max|cpu| =", err)
+    assert err < 1e-6
 
 
 def test_low_margin_draws_compressed_gpu_vs_direct():

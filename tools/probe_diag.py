@@ -44,22 +44,11 @@ def main():
             errs.append((i, float("nan")))
             continue
         pinv = _t64(pf, eng.device).reshape(1, -1)
-        c = blk.comp
         fpA = torch.zeros((1, F), dtype=torch.float64, device=eng.device)
         fpB = torch.zeros_like(fpA)
-        phi_var = (1.0 / (pinv[:, c["var"]] - c["delta0"][None, :])).contiguous()
-        if eng._use_hip:
-            from fastfp_amd import ops
-
-            ops.chol_trsm_fp_accum(c["G"], phi_var, c["K"], c["M0"], c["N0"],
-                                   fpA, gsign=-1.0)
-            ops.chol_trsm_fp_accum(blk.TNT, pinv.contiguous(), blk.RHS,
-                                   blk.sNs, blk.sNr, fpB, gsign=1.0)
-        else:
-            sigc = c["G"][None, :, :] + torch.diag_embed(phi_var)
-            eng._accum_eager_mats(sigc, c["K"], c["M0"], c["N0"], fpA, -1.0)
-            sigma = blk.TNT[None, :, :] + torch.diag_embed(pinv)
-            eng._accum_eager(blk, sigma, fpB)
+        for system, out in ((blk.comp, fpA), (blk.direct, fpB)):
+            eng._accumulate(
+                system, system.diag(pinv[:, system.var]).contiguous(), out)
         scale = fpB.abs().max().clamp_min(1e-30)
         errs.append((i, float((fpA - fpB).abs().max() / scale)))
 
