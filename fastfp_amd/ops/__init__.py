@@ -86,7 +86,7 @@ def _basis_rhs(A, weights, toas, TNr, freqs):
     mp = pad16(m)  # sbgemm is M-tiled: no 128 cap on the basis size
     RHS = torch.zeros((mp, 2 * F + 1), dtype=torch.float64, device=A.device)
     F2 = 2 * F
-    ctiles = (F2 + 63) // 64
+    ctiles = max(1, (F2 + 63) // 64)  # F = 0: sbgemm returns at once
     # split K to fill the 256-CU chip when the frequency grid is small;
     # partial planes + a deterministic torch reduction keep fp64
     # bitwise-reproducible (no atomics)

@@ -8,24 +8,24 @@
 #include <hip/hip_runtime.h>
 
 extern "C" {
-void launch_sigdots(const double*, const double*, const double*,
-                    const double*, int, int, double*, double*, hipStream_t);
-void launch_sbgemm(const double*, const double*, const double*,
-                   const double*, int, int, int, int, double*, long, long,
-                   int, hipStream_t);
-void launch_chol_batch(const double*, const double*, int, int, int, int,
-                       double*, double*, hipStream_t);
-void launch_trsm_fp(const double*, const double*, const double*,
-                    const double*, const double*, int, int, int, int,
-                    double, double*, hipStream_t);
-void launch_sigdots_block(const double*, const double*, const double*,
-                          const double*, const double*, const long*,
-                          const long*, int, int, int, double*, double*,
-                          hipStream_t);
-void launch_diag_inv(const double*, int, long, double*, hipStream_t);
-void launch_trsm_prods(const double*, const double*, const double*,
-                       const double*, const double*, int, int, int, int,
-                       double, double*, hipStream_t);
+int launch_sigdots(const double*, const double*, const double*,
+                   const double*, int, int, double*, double*, hipStream_t);
+int launch_sbgemm(const double*, const double*, const double*,
+                  const double*, int, int, int, int, double*, long, long,
+                  int, hipStream_t);
+int launch_chol_batch(const double*, const double*, int, int, int, int,
+                      double*, double*, hipStream_t);
+int launch_trsm_fp(const double*, const double*, const double*,
+                   const double*, const double*, int, int, int, int,
+                   double, double*, hipStream_t);
+int launch_sigdots_block(const double*, const double*, const double*,
+                         const double*, const double*, const long*,
+                         const long*, int, int, int, double*, double*,
+                         hipStream_t);
+int launch_diag_inv(const double*, int, long, double*, hipStream_t);
+int launch_trsm_prods(const double*, const double*, const double*,
+                      const double*, const double*, int, int, int, int,
+                      double, double*, hipStream_t);
 int fe_max_pulsars();
 int launch_fe_assemble(const double*, const double*, int, int, int, int,
                        double*, hipStream_t);
@@ -45,6 +45,14 @@ hipStream_t stream() {
   return at::hip::getCurrentHIPStream().stream();
 }
 
+// Every launcher returns its hipError_t as an int: an unsupported solve
+// dimension or a rejected launch raises instead of leaving the outputs
+// unwritten.
+void check_launch(int err, const char* what) {
+  TORCH_CHECK(err == 0, what, " launch failed: ",
+              hipGetErrorString((hipError_t)err));
+}
+
 }  // namespace
 
 // sigdots: (toas, ninv, nr (ntoa,), freqs (F,)) -> sNs (3,F), sNr (2,F)
@@ -57,11 +65,16 @@ std::vector<torch::Tensor> sigdots(torch::Tensor toas, torch::Tensor ninv,
   const int ntoa = toas.size(0);
   const int F = freqs.size(0);
   auto opts = toas.options();
+  // no frequencies: empty outputs; no TOAs: every dot is an empty sum
+  if (F == 0 || ntoa == 0)
+    return {torch::zeros({3, F}, opts), torch::zeros({2, F}, opts)};
   auto sNs = torch::empty({3, F}, opts);
   auto sNr = torch::empty({2, F}, opts);
-  launch_sigdots(toas.data_ptr<double>(), ninv.data_ptr<double>(),
-                 nr.data_ptr<double>(), freqs.data_ptr<double>(), ntoa, F,
-                 sNs.data_ptr<double>(), sNr.data_ptr<double>(), stream());
+  check_launch(
+      launch_sigdots(toas.data_ptr<double>(), ninv.data_ptr<double>(),
+                     nr.data_ptr<double>(), freqs.data_ptr<double>(), ntoa, F,
+                     sNs.data_ptr<double>(), sNr.data_ptr<double>(), stream()),
+      "sigdots");
   return {sNs, sNr};
 }
 
@@ -78,10 +91,18 @@ void sbgemm(torch::Tensor T, torch::Tensor toas, torch::Tensor ninv,
   const int m = T.size(1);
   const int F2 = 2 * freqs.size(0);
   TORCH_CHECK(mp % 16 == 0 && mp >= m, "bad mp");  // M-tiled: no upper cap
-  launch_sbgemm(T.data_ptr<double>(), toas.data_ptr<double>(),
-                ninv.data_ptr<double>(), freqs.data_ptr<double>(), ntoa, m,
-                (int)mp, F2, out.data_ptr<double>(), plane_stride, ldo,
-                (int)ksplit, stream());
+  TORCH_CHECK(ksplit >= 1, "ksplit must be >= 1");
+  if (F2 == 0 || mp == 0) return;  // nothing to write
+  if (ntoa == 0) {  // empty K sum: the kernel would store zeros
+    out.zero_();
+    return;
+  }
+  check_launch(
+      launch_sbgemm(T.data_ptr<double>(), toas.data_ptr<double>(),
+                    ninv.data_ptr<double>(), freqs.data_ptr<double>(), ntoa, m,
+                    (int)mp, F2, out.data_ptr<double>(), plane_stride, ldo,
+                    (int)ksplit, stream()),
+      "sbgemm");
 }
 
 // chol_batch_into: TNT (m,m) or (P,m,m), phiinv (D,m) or (P,D,m) ->
@@ -100,14 +121,17 @@ void chol_batch_into(torch::Tensor TNT, torch::Tensor phiinv, int64_t mp,
   const int D = phiinv.size(batched ? 1 : 0);
   TORCH_CHECK(phiinv.dim() == (batched ? 3 : 2), "phiinv rank");
   TORCH_CHECK(phiinv.size(batched ? 2 : 1) == m, "phiinv width != m");
-  TORCH_CHECK(mp % 16 == 0 && mp <= 128 && mp >= m, "mp");
+  TORCH_CHECK(mp % 16 == 0 && mp >= 16 && mp <= 128 && mp >= m, "mp");
   TORCH_CHECK(L.size(0) == (long)P * D && L.size(1) == mp && L.size(2) == mp,
               "L shape");
   TORCH_CHECK(invd.size(0) == (long)P * D && invd.size(1) == mp / 16,
               "invd shape");
-  launch_chol_batch(TNT.data_ptr<double>(), phiinv.data_ptr<double>(), m,
-                    (int)mp, D, P, L.data_ptr<double>(),
-                    invd.data_ptr<double>(), stream());
+  if (D == 0 || P == 0) return;  // empty batch: nothing to factor
+  check_launch(
+      launch_chol_batch(TNT.data_ptr<double>(), phiinv.data_ptr<double>(), m,
+                        (int)mp, D, P, L.data_ptr<double>(),
+                        invd.data_ptr<double>(), stream()),
+      "chol_batch");
 }
 
 // chol_batch: allocate L/invd and factor into them.
@@ -116,7 +140,7 @@ std::vector<torch::Tensor> chol_batch(torch::Tensor TNT, torch::Tensor phiinv,
   const bool batched = TNT.dim() == 3;
   const int m = TNT.size(batched ? 1 : 0);
   TORCH_CHECK(phiinv.dim() == (batched ? 3 : 2), "phiinv rank");
-  TORCH_CHECK(mp % 16 == 0 && mp <= 128 && mp >= m,
+  TORCH_CHECK(mp % 16 == 0 && mp >= 16 && mp <= 128 && mp >= m,
               "chol_batch requires m <= 128 (solve dimension); got m=", m);
   const long n = (batched ? TNT.size(0) : 1) * phiinv.size(batched ? 1 : 0);
   auto L = torch::empty({n, mp, mp}, TNT.options());
@@ -178,12 +202,15 @@ void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                    torch::Tensor sNs, torch::Tensor sNr, torch::Tensor fp,
                    double gsign) {
   const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, fp, "fp", 0);
-  TORCH_CHECK(d.mp % 16 == 0 && d.mp <= 256,
-              "mp must be <=256, multiple of 16");
-  launch_trsm_fp(L.data_ptr<double>(), invd.data_ptr<double>(),
-                 RHS.data_ptr<double>(), sNs.data_ptr<double>(),
-                 sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
-                 fp.data_ptr<double>(), stream());
+  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 256,
+              "mp must be 16..256, multiple of 16");
+  if (d.D == 0 || d.F == 0 || d.P == 0) return;
+  check_launch(
+      launch_trsm_fp(L.data_ptr<double>(), invd.data_ptr<double>(),
+                     RHS.data_ptr<double>(), sNs.data_ptr<double>(),
+                     sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
+                     fp.data_ptr<double>(), stream()),
+      "trsm_fp_accum");
 }
 
 // trsm_prods: the same solve as trsm_fp_accum, but the five corrected
@@ -198,11 +225,13 @@ void trsm_prods(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
               "trsm_prods supports a padded solve dimension mp <= 128 "
               "(multiple of 16); got mp=", d.mp,
               " — use FpEngine.sweep_products for larger bases");
-  if (d.D == 0 || d.F == 0) return;
-  launch_trsm_prods(L.data_ptr<double>(), invd.data_ptr<double>(),
-                    RHS.data_ptr<double>(), sNs.data_ptr<double>(),
-                    sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
-                    out.data_ptr<double>(), stream());
+  if (d.D == 0 || d.F == 0 || d.P == 0) return;
+  check_launch(
+      launch_trsm_prods(L.data_ptr<double>(), invd.data_ptr<double>(),
+                        RHS.data_ptr<double>(), sNs.data_ptr<double>(),
+                        sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
+                        out.data_ptr<double>(), stream()),
+      "trsm_prods");
 }
 
 namespace {
@@ -271,8 +300,10 @@ torch::Tensor diag_inv(torch::Tensor L) {
   const int mp = L.size(1);
   TORCH_CHECK(mp % 16 == 0, "mp multiple of 16");
   auto invd = torch::empty({B, mp / 16, 16, 16}, L.options());
-  launch_diag_inv(L.data_ptr<double>(), mp, B * (mp / 16),
-                  invd.data_ptr<double>(), stream());
+  if (B == 0 || mp == 0) return invd;  // no blocks
+  check_launch(launch_diag_inv(L.data_ptr<double>(), mp, B * (mp / 16),
+                               invd.data_ptr<double>(), stream()),
+               "diag_inv");
   return invd;
 }
 
@@ -292,14 +323,18 @@ std::vector<torch::Tensor> sigdots_block(torch::Tensor toas, torch::Tensor uvec,
   const int F = freqs.size(0);
   const int nblk = sizes.size(0);
   auto opts = toas.options();
+  if (F == 0 || ntoa == 0)
+    return {torch::zeros({3, F}, opts), torch::zeros({2, F}, opts)};
   auto sNs = torch::empty({3, F}, opts);
   auto sNr = torch::empty({2, F}, opts);
-  launch_sigdots_block(toas.data_ptr<double>(), uvec.data_ptr<double>(),
-                       nr.data_ptr<double>(), freqs.data_ptr<double>(),
-                       beta.data_ptr<double>(), offsets.data_ptr<long>(),
-                       sizes.data_ptr<long>(), nblk, ntoa, F,
-                       sNs.data_ptr<double>(), sNr.data_ptr<double>(),
-                       stream());
+  check_launch(
+      launch_sigdots_block(toas.data_ptr<double>(), uvec.data_ptr<double>(),
+                           nr.data_ptr<double>(), freqs.data_ptr<double>(),
+                           beta.data_ptr<double>(), offsets.data_ptr<long>(),
+                           sizes.data_ptr<long>(), nblk, ntoa, F,
+                           sNs.data_ptr<double>(), sNr.data_ptr<double>(),
+                           stream()),
+      "sigdots_block");
   return {sNs, sNr};
 }
 

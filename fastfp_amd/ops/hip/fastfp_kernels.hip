@@ -963,31 +963,35 @@ extern "C" __global__ __launch_bounds__(256) void sigdots_block_kernel(
 }
 
 // ---------------------------------------------------------------------
-// host-side launchers (called from bindings.cpp)
+// host-side launchers (called from bindings.cpp).  Each returns the
+// hipError_t of its launch as an int (0 = success); a solve dimension
+// with no instantiation is hipErrorInvalidValue, never a silent no-op.
 // ---------------------------------------------------------------------
 extern "C" {
 
-void launch_sigdots(const double* toas, const double* ninv, const double* nr,
-                    const double* freqs, int ntoa, int F, double* sNs,
-                    double* sNr, hipStream_t stream) {
+int launch_sigdots(const double* toas, const double* ninv, const double* nr,
+                   const double* freqs, int ntoa, int F, double* sNs,
+                   double* sNr, hipStream_t stream) {
   hipLaunchKernelGGL(sigdots_kernel, dim3(F), dim3(256), 0, stream, toas,
                      ninv, nr, freqs, ntoa, F, sNs, sNr);
+  return (int)hipGetLastError();
 }
 
-void launch_sbgemm(const double* T, const double* toas, const double* ninv,
-                   const double* freqs, int ntoa, int m, int mp, int F2,
-                   double* out, long plane_stride, long ldo, int ksplit,
-                   hipStream_t stream) {
+int launch_sbgemm(const double* T, const double* toas, const double* ninv,
+                  const double* freqs, int ntoa, int m, int mp, int F2,
+                  double* out, long plane_stride, long ldo, int ksplit,
+                  hipStream_t stream) {
   const int ctiles = (F2 + 63) / 64;
   const int mtiles = (mp + FASTFP_MAXMP - 1) / FASTFP_MAXMP;
   hipLaunchKernelGGL(sbgemm_kernel, dim3(ctiles, ksplit, mtiles), dim3(512),
                      0, stream, T, toas, ninv, freqs, ntoa, m, mp, F2, out,
                      plane_stride, ldo);
+  return (int)hipGetLastError();
 }
 
-void launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
-                       int D, int P, double* L, double* invd,
-                       hipStream_t stream) {
+int launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
+                      int D, int P, double* L, double* invd,
+                      hipStream_t stream) {
   // small matrices: 256 threads -> 4 workgroups/CU despite the 115-VGPR
   // diagonal-factor pressure; large: 512 threads for MFMA coverage
   const dim3 grid(D, P), blk(mp <= 64 ? 256 : 512);
@@ -998,13 +1002,15 @@ void launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
     CHOL_CASE(1) CHOL_CASE(2) CHOL_CASE(3) CHOL_CASE(4)
     CHOL_CASE(5) CHOL_CASE(6) CHOL_CASE(7) CHOL_CASE(8)
 #undef CHOL_CASE
+    default: return (int)hipErrorInvalidValue;
   }
+  return (int)hipGetLastError();
 }
 
-void launch_trsm_fp(const double* L, const double* invd, const double* RHS,
-                    const double* sNs, const double* sNr, int mp, int F,
-                    int D, int P, double gsign, double* fp,
-                    hipStream_t stream) {
+int launch_trsm_fp(const double* L, const double* invd, const double* RHS,
+                   const double* sNs, const double* sNr, int mp, int F,
+                   int D, int P, double gsign, double* fp,
+                   hipStream_t stream) {
   const int ftiles = (F + FPT_FREQS - 1) / FPT_FREQS;
   const dim3 grid(ftiles, D, P), blk(512);
   switch (mp >> 4) {
@@ -1025,15 +1031,17 @@ void launch_trsm_fp(const double* L, const double* invd, const double* RHS,
     TRSM_BIG_CASE(9) TRSM_BIG_CASE(10) TRSM_BIG_CASE(11) TRSM_BIG_CASE(12)
     TRSM_BIG_CASE(13) TRSM_BIG_CASE(14) TRSM_BIG_CASE(15) TRSM_BIG_CASE(16)
 #undef TRSM_BIG_CASE
+    default: return (int)hipErrorInvalidValue;
   }
+  return (int)hipGetLastError();
 }
 
 
 // Products mode (Fe): one launch over (ftiles, D, P), mp <= 128.
-void launch_trsm_prods(const double* L, const double* invd, const double* RHS,
-                       const double* sNs, const double* sNr, int mp, int F,
-                       int D, int P, double gsign, double* out,
-                       hipStream_t stream) {
+int launch_trsm_prods(const double* L, const double* invd, const double* RHS,
+                      const double* sNs, const double* sNr, int mp, int F,
+                      int D, int P, double gsign, double* out,
+                      hipStream_t stream) {
   const int ftiles = (F + FPT_FREQS - 1) / FPT_FREQS;
   const dim3 blk(512);
   const dim3 grid(ftiles, D, P);
@@ -1046,23 +1054,27 @@ void launch_trsm_prods(const double* L, const double* invd, const double* RHS,
     TRSM_PRODS_CASE(4) TRSM_PRODS_CASE(5) TRSM_PRODS_CASE(6)
     TRSM_PRODS_CASE(7) TRSM_PRODS_CASE(8)
 #undef TRSM_PRODS_CASE
+    default: return (int)hipErrorInvalidValue;
   }
+  return (int)hipGetLastError();
 }
 
-void launch_diag_inv(const double* L, int mp, long nblk_total, double* invd,
-                     hipStream_t stream) {
+int launch_diag_inv(const double* L, int mp, long nblk_total, double* invd,
+                    hipStream_t stream) {
   hipLaunchKernelGGL(diag_inv_kernel, dim3((nblk_total + 7) / 8), dim3(512),
                      0, stream, L, mp, nblk_total, invd);
+  return (int)hipGetLastError();
 }
 
-void launch_sigdots_block(const double* toas, const double* uvec,
-                          const double* nr, const double* freqs,
-                          const double* beta, const long* offsets,
-                          const long* sizes, int nblk, int ntoa, int F,
-                          double* sNs, double* sNr, hipStream_t stream) {
+int launch_sigdots_block(const double* toas, const double* uvec,
+                         const double* nr, const double* freqs,
+                         const double* beta, const long* offsets,
+                         const long* sizes, int nblk, int ntoa, int F,
+                         double* sNs, double* sNr, hipStream_t stream) {
   hipLaunchKernelGGL(sigdots_block_kernel, dim3(F), dim3(256), 0, stream,
                      toas, uvec, nr, freqs, beta, offsets, sizes,
                      nblk, ntoa, F, sNs, sNr);
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

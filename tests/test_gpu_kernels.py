@@ -111,7 +111,7 @@ def test_chol_batch_vs_torch(m, mp):
         )
 
 
-@pytest.mark.parametrize("m", [37, 120])  # DPG=2 and direct NBT=8 paths
+@pytest.mark.parametrize("m", [37, 120])  # NBT=3 and NBT=8 (only DPG=1 exists)
 def test_trsm_fp_accum_vs_eager(m):
     from fastfp_amd import ops
 
