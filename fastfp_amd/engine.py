@@ -701,12 +701,22 @@ class FpEngine:
             else:
                 pp = torch.empty((P, hi - lo, F), dtype=torch.float64,
                                  device=dev)
-            pp.zero_()
-            solve(Lb[b], Ib[b], lo, hi, pp)
+            solve(Lb[b], Ib[b], lo, hi, pp)  # writes every entry of pp
             fp[lo:hi] += pp.sum(dim=0)
             ev2 = torch.cuda.Event()
             ev2.record(main)
             solve_done[b] = ev2
+
+    # Fewest draws in a chunk for which the stacked sweep solves with
+    # the draw-looping kernel (trsm_fp_store, mp <= 64); below it the
+    # one-draw-per-workgroup kernel runs.  docs/TUNING_NOTES.md has the
+    # measurement behind the value.
+    DRAW_LOOP_MIN_DRAWS = 16
+    DRAW_LOOP_MAX_MP = 64
+
+    def _draw_loop_solve(self, mp: int, ndraws: int) -> bool:
+        return (mp <= self.DRAW_LOOP_MAX_MP
+                and ndraws >= self.DRAW_LOOP_MIN_DRAWS)
 
     def _stacked_chunks(self, st: SolveSystem, rows, draw_chunk):
         """Draw chunks of a stacked sweep: the ``(lo, hi)`` list and a
@@ -741,8 +751,13 @@ class FpEngine:
 
             def solve(L, invd, lo, hi, pp):
                 n = P * (hi - lo)
-                ext.trsm_fp_accum(L[:n], invd[:n], st.RHS, st.S, st.R, pp,
-                                  st.gsign)
+                if self._draw_loop_solve(mp, hi - lo):
+                    ext.trsm_fp_store(L[:n], invd[:n], st.RHS, st.S, st.R,
+                                      pp, st.gsign)
+                else:
+                    pp.zero_()
+                    ext.trsm_fp_accum(L[:n], invd[:n], st.RHS, st.S, st.R,
+                                      pp, st.gsign)
 
             self._pipeline_chunks(chunks, P, mp, F, fp, fp_pp,
                                   factor_into, solve)
@@ -755,9 +770,13 @@ class FpEngine:
             else:  # tail chunk: a dim-1 slice would be non-contiguous
                 pp = torch.empty((P, hi - lo, F), dtype=torch.float64,
                                  device=self.device)
-            pp.zero_()
-            ops.chol_trsm_fp_accum(st.A, d, st.RHS, st.S, st.R, pp,
-                                   gsign=st.gsign)
+            if self._draw_loop_solve(mp, hi - lo):
+                L, invd = ext.chol_batch(st.A, d, mp)
+                ext.trsm_fp_store(L, invd, st.RHS, st.S, st.R, pp, st.gsign)
+            else:
+                pp.zero_()
+                ops.chol_trsm_fp_accum(st.A, d, st.RHS, st.S, st.R, pp,
+                                       gsign=st.gsign)
             fp[lo:hi] += pp.sum(dim=0)
 
     def sweep_products(self, sigmas=None, phiinvs=None) -> torch.Tensor:

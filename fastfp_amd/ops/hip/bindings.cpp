@@ -18,6 +18,10 @@ int launch_chol_batch(const double*, const double*, int, int, int, int,
 int launch_trsm_fp(const double*, const double*, const double*,
                    const double*, const double*, int, int, int, int,
                    double, double*, hipStream_t);
+int launch_trsm_fp_draws(const double*, const double*, const double*,
+                         const double*, const double*, int, int, int, int,
+                         double, double*, int, int, hipStream_t);
+int trsm_fp_draws_tile_freqs();
 int launch_sigdots_block(const double*, const double*, const double*,
                          const double*, const double*, const long*,
                          const long*, int, int, int, double*, double*,
@@ -213,6 +217,36 @@ void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
       "trsm_fp_accum");
 }
 
+// trsm_fp_store: the same solve and reduction as trsm_fp_accum for
+// mp <= 64, by the draw-looping kernel: a workgroup keeps its RHS tile
+// in registers over `draws_per_block` consecutive draws (0: sized from
+// the device's resident workgroup slots).  Plain stores: every entry of
+// `out` (D,F) / (P,D,F) is written and none is read, so `out` need not
+// be initialised; the values equal trsm_fp_accum into zeros bit for bit.
+void trsm_fp_store(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
+                   torch::Tensor sNs, torch::Tensor sNr, torch::Tensor out,
+                   double gsign, int64_t draws_per_block) {
+  const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, out, "out", 0);
+  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 64,
+              "trsm_fp_store supports a padded solve dimension mp <= 64 "
+              "(multiple of 16); got mp=", d.mp, " — use trsm_fp_accum");
+  TORCH_CHECK(draws_per_block >= 0 && draws_per_block < (1L << 31),
+              "draws_per_block must be >= 0");
+  if (d.D == 0 || d.F == 0 || d.P == 0) return;
+  // the factor is fetched with 16-byte loads
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(L.data_ptr<double>()) |
+               reinterpret_cast<uintptr_t>(invd.data_ptr<double>())) % 16 == 0,
+              "L and invd must be 16-byte aligned");
+  const int ncu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  check_launch(
+      launch_trsm_fp_draws(L.data_ptr<double>(), invd.data_ptr<double>(),
+                           RHS.data_ptr<double>(), sNs.data_ptr<double>(),
+                           sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
+                           out.data_ptr<double>(), (int)draws_per_block, ncu,
+                           stream()),
+      "trsm_fp_store");
+}
+
 // trsm_prods: the same solve as trsm_fp_accum, but the five corrected
 // products [ss, cc, sc, sr, cr] are stored un-collapsed: out (D,5,F)
 // for a single pulsar, (P,D,5,F) pulsar-batched.  Plain stores — `out`
@@ -350,6 +384,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "chol_batch into caller-owned L/invd (pipeline buffers)");
   m.def("trsm_fp_accum", &trsm_fp_accum,
         "batched TRSM + fused 2x2 Fp reduction");
+  m.def("trsm_fp_store", &trsm_fp_store,
+        "draw-looping TRSM + fused 2x2 Fp reduction, plain stores (mp <= 64)",
+        py::arg("L"), py::arg("invd"), py::arg("RHS"), py::arg("sNs"),
+        py::arg("sNr"), py::arg("out"), py::arg("gsign"),
+        py::arg("draws_per_block") = 0);
+  m.def("trsm_fp_store_tile_freqs", &trsm_fp_draws_tile_freqs,
+        "frequencies per workgroup tile of trsm_fp_store");
   m.def("trsm_prods", &trsm_prods,
         "batched TRSM storing the five corrected products (Fe input)");
   m.def("fe_assemble", &fe_assemble,

@@ -27,6 +27,10 @@
 //                        utils.py:54 + fastfp.py:81-90); its products
 //                        mode stores the five corrected products
 //                        instead of Fp (the Fe input).  mp <= 128
+//   trsm_fp_draws_kernel — the same solve for mp <= 64 with the loop
+//                        over draws inside the workgroup: the RHS tile
+//                        stays on chip over a slice of draws, Fp is a
+//                        plain store (the stacked compressed sweep)
 //   trsm_fp_rl_kernel  — right-looking form of the same solve, the
 //                        path for 128 < mp <= 256
 //   diag_inv_kernel    — inverted 16x16 diagonal blocks of a rocSOLVER
@@ -53,10 +57,13 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include <algorithm>
+
 #define FASTFP_MAXMP 128
 #define NB 16  // Cholesky/TRSM block size (one MFMA tile)
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
+typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 #define MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 
@@ -453,6 +460,24 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
 #define FPT_FREQS 63
 #define NBMAX (FASTFP_MAXMP / 16)
 
+// The 2x2 closure of one frequency: corrected products from the
+// reduced dots, then Fp = 0.5 N^T M^-1 N in closed form.  One function
+// for trsm_fp_kernel and trsm_fp_draws_kernel, so both emit the same
+// operations and their results agree bit for bit.
+static __device__ __forceinline__ double fp_close(
+    double s11, double s22, double s12, double r1, double r2, double gsign,
+    double ss, double cc, double sc, double su, double cu) {
+  const double M11 = s11 - gsign * ss;
+  const double M22 = s22 - gsign * cc;
+  const double M12 = s12 - gsign * sc;
+  const double N1 = r1 - gsign * su;
+  const double N2 = r2 - gsign * cu;
+  const double det = fma(M11, M22, -M12 * M12);
+  const double num =
+      fma(N1 * N1, M22, fma(-2.0 * N1, N2 * M12, N2 * N2 * M11));
+  return 0.5 * num / det;
+}
+
 // PRODS: products mode for the sky-coherent Fe statistic — the
 // epilogue stores the five corrected products [M11, M22, M12, N1, N2]
 // = [s|s, c|c, s|c, s|r, c|r] un-collapsed into
@@ -647,25 +672,272 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
     const int q = (jw + li) >> 1;  // frequency index within the block
     if (lk == 0 && (li & 1) == 0 && q < FPT_FREQS && f0 + q < F) {
       const int f = f0 + q;
-      const double M11 = sNs[f] - gsign * a1;
-      const double M22 = sNs[F + f] - gsign * b1;
-      const double M12 = sNs[2 * F + f] - gsign * a3;
-      const double N1 = sNr[f] - gsign * a2;
-      const double N2 = sNr[F + f] - gsign * b2;
       if constexpr (PRODS) {
         double* o = fp_all + (((long)pp * D + (d0 + e)) * 5) * F + f;
-        o[0] = M11;
-        o[F] = M22;
-        o[2L * F] = M12;
-        o[3L * F] = N1;
-        o[4L * F] = N2;
+        o[0] = sNs[f] - gsign * a1;
+        o[F] = sNs[F + f] - gsign * b1;
+        o[2L * F] = sNs[2 * F + f] - gsign * a3;
+        o[3L * F] = sNr[f] - gsign * a2;
+        o[4L * F] = sNr[F + f] - gsign * b2;
       } else {
-        const double det = fma(M11, M22, -M12 * M12);
-        const double num =
-            fma(N1 * N1, M22, fma(-2.0 * N1, N2 * M12, N2 * N2 * M11));
-        fp[(long)(d0 + e) * F + f] += 0.5 * num / det;
+        fp[(long)(d0 + e) * F + f] +=
+            fp_close(sNs[f], sNs[F + f], sNs[2 * F + f], sNr[f], sNr[F + f],
+                     gsign, a1, b1, a3, a2, b2);
       }
     }
+  }
+}
+
+// ---------------------------------------------------------------------
+// trsm_fp_draws: the solve and reduction of trsm_fp_kernel<NBT,1> with
+// the loop over DRAWS inside the workgroup.  A workgroup owns one
+// (pulsar, frequency tile, draw slice [dlo, dhi)): its RHS strip (in
+// registers) and its sNs/sNr entries (in LDS) are loaded ONCE and every
+// draw of the slice is solved from them, so the per-draw traffic is the
+// factor alone.  Draw d+1's factor is fetched into registers before
+// draw d's MFMAs and written to the other LDS buffer after them: one
+// barrier per draw.  fp[p, d, f] is a plain store and is never read.
+// NBT 1..4 (mp <= 64).
+//
+// Same numbers as trsm_fp_kernel accumulating into zeros, bit for bit:
+// the MFMA order per column, the acc/acc2 split, the order of every fma
+// chain of the lane-split reduction and fp_close are its own.  Three
+// things differ in form only:
+//   * the strict-lower panels are staged NEGATED and acc starts at +RHS,
+//     so acc holds the exact negative of trsm_fp_kernel's (every fma of
+//     the chain is sign-symmetric) and the diagonal solve takes it as it
+//     is — no negation of 8 + 8 registers per row block per draw;
+//   * the w*w and w*partner sums of row block rb are taken as soon as
+//     W[rb] exists, in the shadow of the next row block's MFMAs; only
+//     the w*u sum waits for the barrier that publishes the u column;
+//   * the partner column (lane ^ 1) comes by DPP, not by an LDS permute.
+//
+// Grid: 1-D, 8 * ceil(P*nsl / 8) * ntile blocks, decoded as
+//   g = bid % 8, j = bid / 8, slice s = (j / ntile) * 8 + g,
+//   tile = j % ntile, pulsar = s / nsl, draws [(s % nsl) * dpb, +dpb)
+// so the ntile tiles of one (pulsar, slice) share bid % 8 — blocks that
+// share an XCD's L2 — and are dispatched together: they walk the same
+// draws and each factor comes from HBM about once.  Placement changes
+// speed only.  Blocks with s >= P*nsl (grid padding) return at once.
+//
+// LDS (one array, 48.5 KiB at NBT=4):
+//   2 buffers x (NBT(NBT-1)/2 strict-lower + NBT inverted-diagonal)
+//     16x16 blocks, rows padded to 18 doubles: the a-fragment read
+//     18*li + lk is conflict-free over a 32-lane half;
+//   2 x mp doubles: the solved u column, by draw parity;
+//   5 x 64 doubles: sNs/sNr of the tile's frequencies.
+// block = 512 (8 waves), tile = 63 frequencies + u as in trsm_fp_kernel.
+// Registers as compiled (gfx950, -O3): NBT=4 128 VGPR, 4 waves/SIMD
+// (two workgroups per CU; 8 bytes of spill, reloaded once per draw); NBT=3
+// 104, NBT=2 72, NBT=1 46.  RHS copy 8*NBT, W 8*NBT, the three
+// accumulators 24, the prefetched factor 4*NBT.
+// ---------------------------------------------------------------------
+#define DL_BS 18              // row stride of a staged block (doubles)
+#define DL_BLK (16 * DL_BS)   // doubles per staged block
+#define DL_FREQS 63           // frequencies per tile
+
+// the value of lane ^ 1 (a frequency's partner column) by DPP
+// quad_perm [1,0,3,2]: a register move, no LDS permute traffic.  Call
+// with all lanes active.
+static __device__ __forceinline__ double pair_swap(double w) {
+  int lo = __double2loint(w), hi = __double2hiint(w);
+  lo = __builtin_amdgcn_update_dpp(0, lo, 0xB1, 0xF, 0xF, true);
+  hi = __builtin_amdgcn_update_dpp(0, hi, 0xB1, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+
+template <int NBT>
+__global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
+    const double* __restrict__ L_all /*(P*D,mp,mp)*/,
+    const double* __restrict__ invd_all /*(P*D, mp/16, 16, 16)*/,
+    const double* __restrict__ RHS_all /*(P, mp, 2F+1)*/,
+    const double* __restrict__ sNs_all /*(P,3,F)*/,
+    const double* __restrict__ sNr_all /*(P,2,F)*/, int F, int D, int P,
+    int dpb /*draws per block*/, int nsl /*slices = ceil(D/dpb)*/,
+    double gsign, double* __restrict__ fp_all /*(P,D,F)*/) {
+  constexpr int mp = NBT * 16;
+  constexpr int UC = 126;  // block column of u
+  constexpr int NLB = NBT * (NBT - 1) / 2;  // strict-lower blocks
+  constexpr int BUF = (NLB + NBT) * DL_BLK;
+  // 16-byte pieces: rb*128 per row panel, NBT*128 of inverted diagonals,
+  // at most one per thread each
+  static_assert(NBT * 128 <= 512, "one prefetch slot per panel");
+  __shared__ __attribute__((aligned(16))) double S[2 * BUF + 2 * mp + 5 * 64];
+
+  const int ntile = (F + DL_FREQS - 1) / DL_FREQS;
+  const int j = blockIdx.x >> 3;
+  const int s = (j / ntile) * 8 + (blockIdx.x & 7);
+  if (s >= P * nsl) return;
+  const int pp = s / nsl;
+  const int dlo = (s % nsl) * dpb;
+  const int dhi = min(D, dlo + dpb);
+  const int f0 = (j % ntile) * DL_FREQS;
+
+  const double* L = L_all + (long)pp * D * mp * mp;
+  const double* invd = invd_all + (long)pp * D * NBT * 256;
+  const double* RHS = RHS_all + (long)pp * mp * (2L * F + 1);
+  const double* sNs = sNs_all + (long)pp * 3 * F;
+  const double* sNr = sNr_all + (long)pp * 2 * F;
+  double* fp = fp_all + (long)pp * D * F;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+  const long ldr = 2L * F + 1;
+  const int jw = wv * 16;      // this wave's 16-column strip
+  const int li = lane & 15;    // a-frag row / strip column
+  const int lk = lane >> 4;    // k index / acc row group
+
+  // factor of draw d -> registers, 16 bytes per thread and panel: the
+  // inverted diagonal blocks, then the strict-lower row panels.  Every
+  // thread loads — past the end of a panel it re-reads the panel's last
+  // piece, which stage() drops — so no load sits behind a branch.
+  // (f64x2, not HIP's double2: an array of that struct is not promoted
+  // to registers.)
+  f64x2 pre[NBT];  // [0]: inverted diagonals, [rb]: row panel rb
+  auto fetch = [&](int d) {
+    const double* Ld = L + (long)d * mp * mp;
+    pre[0] = reinterpret_cast<const f64x2*>(
+        invd + (long)d * NBT * 256)[min(tid, NBT * 128 - 1)];
+#pragma unroll
+    for (int rb = 1; rb < NBT; ++rb) {
+      const int idx = min(tid, rb * 128 - 1);
+      const int r = idx / (rb * 8), c = 2 * (idx % (rb * 8));
+      pre[rb] =
+          *reinterpret_cast<const f64x2*>(Ld + (rb * 16 + r) * mp + c);
+    }
+  };
+  // registers -> LDS buffer `buf` (same index walk as fetch); the row
+  // panels negated
+  auto stage = [&](double* buf) {
+    if (tid < NBT * 128)
+      *reinterpret_cast<f64x2*>(buf + (NLB + (tid >> 7)) * DL_BLK +
+                                ((tid >> 3) & 15) * DL_BS + 2 * (tid & 7)) =
+          pre[0];
+#pragma unroll
+    for (int rb = 1; rb < NBT; ++rb) {
+      if (tid < rb * 128) {
+        const int r = tid / (rb * 8), c = 2 * (tid % (rb * 8));
+        *reinterpret_cast<f64x2*>(buf +
+                                  (rb * (rb - 1) / 2 + (c >> 4)) * DL_BLK +
+                                  r * DL_BS + (c & 15)) = -pre[rb];
+      }
+    }
+  };
+
+  fetch(dlo);
+
+  // this wave's RHS strip, acc layout, kept for the whole slice:
+  // R0[rt][v] = RHS[row = rt*16 + 4v + lk][block-col jw + li]
+  const int bc = jw + li;
+  f64x4 R0[NBT];
+#pragma unroll
+  for (int rt = 0; rt < NBT; ++rt) {
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const long row = rt * 16 + 4 * v + lk;
+      double val = 0.0;
+      if (bc < UC) {
+        const long gc = 2L * f0 + bc;
+        if (gc < 2L * F) val = RHS[row * ldr + gc];
+      } else if (bc == UC) {
+        val = RHS[row * ldr + 2L * F];  // the u column
+      }
+      R0[rt][v] = val;
+    }
+  }
+  // the tile's sNs/sNr entries: Sc[i][q], q = frequency within the tile
+  double* Sc = S + 2 * BUF + 2 * mp;
+  if (tid < 64) {
+    const bool live = tid < DL_FREQS && f0 + tid < F;
+    const int fq = live ? f0 + tid : 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      Sc[i * 64 + tid] = live ? sNs[i * F + fq] : 0.0;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      Sc[(3 + i) * 64 + tid] = live ? sNr[i * F + fq] : 0.0;
+  }
+  const int q = bc >> 1;  // frequency index within the tile
+  const int f = f0 + q;
+  // the lane that closes frequency q
+  const bool closer = lk == 0 && (li & 1) == 0 && q < DL_FREQS && f < F;
+
+  stage(S);
+  __syncthreads();
+
+  const int aoff = li * DL_BS + lk;  // a-fragment offset inside a block
+  for (int d = dlo; d < dhi; ++d) {
+    const int b = (d - dlo) & 1;
+    const double* Sb = S + b * BUF;
+    double* Wu = S + 2 * BUF + b * mp;
+    const bool more = d + 1 < dhi;
+    if (more) fetch(d + 1);
+
+    // blocked forward substitution from the register RHS copy; acc is
+    // the negative of trsm_fp_kernel's (negated panels)
+    f64x4 W[NBT];
+    double a1 = 0, a2 = 0, a3 = 0;
+#pragma unroll
+    for (int rb = 0; rb < NBT; ++rb) {
+      f64x4 acc = R0[rb];
+      f64x4 acc2 = f64x4{0, 0, 0, 0};
+#pragma unroll
+      for (int cb = 0; cb < rb; ++cb) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          const double a =
+              Sb[(rb * (rb - 1) / 2 + cb) * DL_BLK + kk * 4 + aoff];
+          if (cb & 1)
+            acc2 = MFMA_F64(a, W[cb][kk], acc2);
+          else
+            acc = MFMA_F64(a, W[cb][kk], acc);
+        }
+      }
+      acc += acc2;
+      f64x4 sol = f64x4{0, 0, 0, 0};
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const double a = Sb[(NLB + rb) * DL_BLK + kk * 4 + aoff];
+        sol = MFMA_F64(a, acc[kk], sol);
+      }
+      W[rb] = sol;
+      // lane-split sums that need no u column (see trsm_fp_kernel)
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const double w = sol[v];
+        const double wp = pair_swap(w);  // partner column
+        a1 = fma(w, w, a1);
+        a3 = fma(w, wp, a3);
+      }
+      // pin the partial sums here: left alone the scheduler sinks all
+      // of them below the barrier and spills the partner values
+      asm volatile("" : "+v"(a1), "+v"(a3));
+    }
+    if (wv == 7 && li == 14) {
+#pragma unroll
+      for (int rt = 0; rt < NBT; ++rt)
+#pragma unroll
+        for (int v = 0; v < 4; ++v) Wu[rt * 16 + 4 * v + lk] = W[rt][v];
+    }
+    if (more) stage(S + (b ^ 1) * BUF);
+    // factor d+1 and u column d visible; every read of buffer b done
+    __syncthreads();
+
+#pragma unroll
+    for (int rt = 0; rt < NBT; ++rt)
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+        a2 = fma(W[rt][v], Wu[rt * 16 + 4 * v + lk], a2);
+    // sum the 4 row groups (lanes lk = 0..3 share li): +16, +32 lanes
+    a1 += __shfl_down(a1, 32, 64); a1 += __shfl_down(a1, 16, 64);
+    a2 += __shfl_down(a2, 32, 64); a2 += __shfl_down(a2, 16, 64);
+    a3 += __shfl_down(a3, 32, 64); a3 += __shfl_down(a3, 16, 64);
+    const double b1 = pair_swap(a1);  // cc (for even lanes)
+    const double b2 = pair_swap(a2);  // cu
+    if (closer)
+      fp[(long)d * F + f] =
+          fp_close(Sc[q], Sc[64 + q], Sc[128 + q], Sc[192 + q], Sc[256 + q],
+                   gsign, a1, b1, a3, a2, b2);
   }
 }
 
@@ -1036,6 +1308,57 @@ int launch_trsm_fp(const double* L, const double* invd, const double* RHS,
   return (int)hipGetLastError();
 }
 
+// frequencies per workgroup tile of the draw-looping solve
+int trsm_fp_draws_tile_freqs() { return DL_FREQS; }
+
+// Draw-looping solve (mp <= 64), plain stores into fp (P,D,F).
+// draws_per_block > 0 forces the slice length (tests); 0 sizes it from
+// the resident workgroup slots (occupancy query x ncu): 64 draws where
+// the launch allows — the one-time RHS load is then under 2% of a
+// slice's traffic — and fewer when that would leave the launch under 8
+// rounds of resident blocks, so the partial last round stays a small
+// fraction; slices are then evened out over D.
+int launch_trsm_fp_draws(const double* L, const double* invd,
+                         const double* RHS, const double* sNs,
+                         const double* sNr, int mp, int F, int D, int P,
+                         double gsign, double* fp, int draws_per_block,
+                         int ncu, hipStream_t stream) {
+  const int ntile = (F + DL_FREQS - 1) / DL_FREQS;
+  int dpb = draws_per_block, nsl = 0;
+  auto plan = [&](auto kern) -> long {
+    if (dpb <= 0) {
+      int per_cu = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512,
+                                                       0) != hipSuccess ||
+          per_cu < 1)
+        per_cu = 1;
+      const long slots = (long)per_cu * ncu;
+      const long units = (long)P * ntile * D;  // (tile, draw) pairs
+      dpb = (int)std::min<long>(64, std::max<long>(1, units / (8 * slots)));
+      dpb = std::min(dpb, D);
+      const int n = (D + dpb - 1) / dpb;
+      dpb = (D + n - 1) / n;
+    }
+    dpb = std::min(dpb, D);
+    nsl = (D + dpb - 1) / dpb;
+    return ((long)P * nsl + 7) / 8 * 8 * ntile;
+  };
+  switch (mp >> 4) {
+#define DRAWS_CASE(NBT) \
+    case NBT: { \
+      auto kern = trsm_fp_draws_kernel<NBT>; \
+      const long nblk = plan(kern); \
+      if (nblk >= (1L << 31)) return (int)hipErrorInvalidValue; \
+      hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), 0, stream, \
+                         L, invd, RHS, sNs, sNr, F, D, P, dpb, nsl, gsign, \
+                         fp); \
+    } break;
+    DRAWS_CASE(1) DRAWS_CASE(2) DRAWS_CASE(3) DRAWS_CASE(4)
+#undef DRAWS_CASE
+    default: return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
+}
 
 // Products mode (Fe): one launch over (ftiles, D, P), mp <= 128.
 int launch_trsm_prods(const double* L, const double* invd, const double* RHS,

@@ -5,6 +5,11 @@ Prints per-kernel wall time and fp64 TFLOP/s at the NMFp bench shape.
 
     python tools/kernel_bench.py fe [P D F nsky m]
 
+    python tools/kernel_bench.py stacked [P D F m]
+
+times the two solve kernels of the stacked compressed sweep
+(trsm_fp_accum, trsm_fp_store); defaults P=67, D=1024, F=1000, m=60.
+
 times the Fe-on-device kernels (trsm_prods, fe_assemble, fe_skymax);
 defaults P=67, D=256, F=200, nsky=768, m=120.
 """
@@ -72,6 +77,8 @@ def main():
         print(f"trsm  D={D:5d}: {t*1e6:9.1f} us  {flops/t/1e12:6.2f} TF/s"
               f"  ({flops:.3g} flops)")
 
+    main_stacked()
+
     # sbgemm at the two headline shapes
     for Fs in (1000, 10000):
         fr = torch.as_tensor(
@@ -88,6 +95,45 @@ def main():
         t = timeit(fn, iters=10)
         flops = 2.0 * mp * 2 * Fs * ntoa
         print(f"sbgemm F={Fs:6d} ks={ks}: {t*1e6:9.1f} us  {flops/t/1e12:6.2f} TF/s")
+
+
+def main_stacked(P=67, D=1024, F=1000, m=60):
+    """The two solve kernels of the stacked compressed sweep, isolated,
+    at the flagship shape (67 pulsars, one 1024-draw chunk, mp = 64):
+    trsm_fp_accum (one draw per workgroup, accumulates) against
+    trsm_fp_store (draw loop, plain stores).  Device events; the factor
+    is real, the outputs are checked bitwise equal."""
+    mp = (m + 15) // 16 * 16
+    ntoa = 2000
+    rng = np.random.default_rng(0)
+    T = torch.as_tensor(rng.normal(size=(P, ntoa, m)), dtype=torch.float64,
+                        device=DEV)
+    TNT = (T.transpose(1, 2) @ T * 1e12).contiguous()  # (P, m, m)
+    del T
+    phiinv = torch.as_tensor(rng.uniform(0.5, 2.0, (P, D, m)) * 1e10,
+                             dtype=torch.float64, device=DEV)
+    RHS = torch.as_tensor(rng.normal(size=(P, mp, 2 * F + 1)) * 1e6,
+                          dtype=torch.float64, device=DEV)
+    RHS[:, m:] = 0.0
+    sNs = torch.ones((P, 3, F), dtype=torch.float64, device=DEV) * 1e13
+    sNr = torch.ones((P, 2, F), dtype=torch.float64, device=DEV)
+    L, invd = ext.chol_batch(TNT, phiinv, mp)
+    flops = P * D * (mp * mp / 2) * (2 * F + 2) * 2
+    acc = torch.zeros((P, D, F), dtype=torch.float64, device=DEV)
+    out = torch.full((P, D, F), float("nan"), dtype=torch.float64,
+                     device=DEV)
+    ext.trsm_fp_accum(L, invd, RHS, sNs, sNr, acc, -1.0)
+    ext.trsm_fp_store(L, invd, RHS, sNs, sNr, out, -1.0)
+    assert torch.equal(acc, out), "trsm_fp_store != trsm_fp_accum into zeros"
+    iters = 20 if D >= 256 else 100
+    t = timeit(lambda: ext.trsm_fp_accum(L, invd, RHS, sNs, sNr, acc, -1.0),
+               iters=iters)
+    print(f"trsm_fp_accum P={P} D={D} F={F} mp={mp}: {t*1e3:9.3f} ms"
+          f"  {flops/t/1e12:6.2f} TF/s")
+    t = timeit(lambda: ext.trsm_fp_store(L, invd, RHS, sNs, sNr, out, -1.0),
+               iters=iters)
+    print(f"trsm_fp_store P={P} D={D} F={F} mp={mp}: {t*1e3:9.3f} ms"
+          f"  {flops/t/1e12:6.2f} TF/s")
 
 
 def main_fe(P=67, D=256, F=200, nsky=768, m=120):
@@ -145,5 +191,7 @@ def main_fe(P=67, D=256, F=200, nsky=768, m=120):
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "fe":
         main_fe(*[int(a) for a in sys.argv[2:]])
+    elif len(sys.argv) > 1 and sys.argv[1] == "stacked":
+        main_stacked(*[int(a) for a in sys.argv[2:]])
     else:
         main()
