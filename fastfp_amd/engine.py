@@ -739,11 +739,14 @@ class FpEngine:
                             device=self.device)
         mp = ops.pad16(st.A.shape[-1])
         if len(chunks) > 1 and mp <= ops.MAX_MP_CHOL:
-            # SOFTWARE PIPELINE across draw chunks: the Cholesky is
-            # latency-bound (~82% parked waves), the solve is
-            # throughput-bound, so chunk k+1's factor runs on a side
-            # stream UNDER chunk k's solve and its parked cycles are
-            # filled with solve work.  Above MAX_MP_CHOL the factor is
+            # SOFTWARE PIPELINE across draw chunks: chunk k+1's factor
+            # runs on a side stream beside chunk k's solve.  The solve
+            # kernels fill the register file (4 waves/SIMD at 128
+            # VGPR), so a CU that takes factor workgroups gives up
+            # solve workgroups for as long as they live: measured, the
+            # step pays about 0.8 of the factor's stand-alone time per
+            # chunk, and the pipeline hides the other fifth
+            # (docs/TUNING_NOTES.md).  Above MAX_MP_CHOL the factor is
             # rocSOLVER's, which does not write into caller buffers.
             def factor_into(L, invd, lo, hi):
                 n = P * (hi - lo)

@@ -228,10 +228,12 @@ extern "C" __global__ __launch_bounds__(512) void sbgemm_kernel(
 // identity padding to mp) in LDS, factor L L^T = Sigma (right-looking,
 // NB=16 blocks, MFMA trailing updates), invert each 16x16 diagonal
 // block, write L (D, mp, mp) and invdiag (D, mp/16, 16, 16).
-// grid.x = D, block = 512 (8 waves).  The 16x16 diagonal factor and its
-// inversion run REGISTER-resident in wave 0 with cross-lane __shfl
-// (width 16) -- the LDS read-modify-write chains of the naive version
-// were the kernel's dominant cost (profiles/r01_initial_stats.md).
+// grid = (D, P), block = 256 (mp <= 64) or 512.  The 16x16 diagonal
+// factor and its inversion run REGISTER-resident in wave 0 with DPP
+// row broadcasts (row_bcast) -- the LDS read-modify-write chains of
+// the naive version were the kernel's dominant cost
+// (profiles/r01_initial_stats.md), and the LDS permutes of the __shfl
+// version that followed it were a third of what remained.
 // ---------------------------------------------------------------------
 // (A (+i)-rotation column swizzle in place of the +1 row pad would
 // shave Ash from 33.3 to 32.0 KB at mp=64 — one more workgroup per CU
@@ -253,6 +255,31 @@ extern "C" __global__ __launch_bounds__(512) void sbgemm_kernel(
 // (Forcing a 6-waves/SIMD allocation target on the small shapes got
 // there only by spilling 44 B/lane and measured neutral — reverted;
 // the no-spill allocation already reaches 5 waves.)
+
+// Lane T of every 16-lane row, broadcast to that row: DPP row_newbcast
+// (control 0x150 + T), a register move where a constant-lane
+// __shfl(.., T, 16) is two LDS-permute round trips.  T must be a
+// compile-time constant after unrolling, hence the switch.  A DPP read
+// of a lane that EXEC masks off returns the bound-control zero, not the
+// lane's value: call with all 64 lanes active.
+static __device__ __forceinline__ double row_bcast(double w, int t) {
+  int lo = __double2loint(w), hi = __double2hiint(w);
+  switch (t) {
+#define ROW_BCAST_CASE(T)                                                  \
+    case T:                                                                \
+      lo = __builtin_amdgcn_update_dpp(0, lo, 0x150 + T, 0xF, 0xF, true);  \
+      hi = __builtin_amdgcn_update_dpp(0, hi, 0x150 + T, 0xF, 0xF, true);  \
+      break;
+    ROW_BCAST_CASE(0) ROW_BCAST_CASE(1) ROW_BCAST_CASE(2) ROW_BCAST_CASE(3)
+    ROW_BCAST_CASE(4) ROW_BCAST_CASE(5) ROW_BCAST_CASE(6) ROW_BCAST_CASE(7)
+    ROW_BCAST_CASE(8) ROW_BCAST_CASE(9) ROW_BCAST_CASE(10) ROW_BCAST_CASE(11)
+    ROW_BCAST_CASE(12) ROW_BCAST_CASE(13) ROW_BCAST_CASE(14)
+    ROW_BCAST_CASE(15)
+#undef ROW_BCAST_CASE
+  }
+  return __hiloint2double(hi, lo);
+}
+
 template <int NBT>
 __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     const double* __restrict__ TNT_all /*(P,m,m)*/,
@@ -293,11 +320,24 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
   __syncthreads();
 
   // Look-ahead right-looking Cholesky: the serial 16x16 diagonal
-  // factor of column kb+1 (wave 0, register/shfl) runs CONCURRENTLY
+  // factor of column kb+1 (wave 0, register/DPP) runs CONCURRENTLY
   // with the MFMA trailing updates of columns kb+2.. (waves 1..7) --
   // the PMC profile showed 84-88% of wave cycles parked waiting on the
   // serial diagonal.  Two inverted-diagonal buffers ping-pong by kb
   // parity.
+  //
+  // The chain has no lane-dependent branch, so every row_bcast runs
+  // with all 64 lanes active, and it issues a quarter fewer
+  // instructions than one select per update.  At step t lane i updates
+  // all of row[t+1..15], not only its lower-triangle entries j <= i.
+  // An entry (i, j > i) then holds a value that means nothing, but it
+  // only ever feeds entries (i, j' > j) of the same kind: a step reads
+  // lane j's row[t] for t <= j alone, and only entries c <= i are
+  // stored.  In the inversion x[t] is an exact +0.0 for t < c, so
+  // fma(lrt, x[t], acc2) leaves acc2 (still +0.0 there) unchanged for
+  // finite lrt and the t >= c select is not needed.  The entries that
+  // are used see the same operations in the same order as under the
+  // selects: L and invd keep every bit.
 #define CHOL_DIAG(KB, DST)                                                   \
   {                                                                          \
     const int dk0 = (KB)*NB;                                                 \
@@ -306,21 +346,23 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     _Pragma("unroll") for (int c = 0; c < 16; ++c) row[c] =                  \
         AS_(dk0 + i, dk0 + c);                                               \
     _Pragma("unroll") for (int t = 0; t < 16; ++t) {                         \
-      const double dv = sqrt(__shfl(row[t], t, 16));                         \
-      const double rdv = 1.0 / dv;                                           \
-      if (i > t) row[t] *= rdv;                                              \
-      else if (i == t) row[t] = dv;                                          \
-      _Pragma("unroll") for (int j = t + 1; j < 16; ++j) {                   \
-        const double ljt = __shfl(row[t], j, 16);                            \
-        if (i >= j) row[j] = fma(-row[t], ljt, row[j]);                      \
-      }                                                                      \
+      const double dv = sqrt(row_bcast(row[t], t));                          \
+      double rdv = 1.0 / dv;                                                 \
+      /* every lane divides: a division kept to the lanes i != t is a  */   \
+      /* branch, and the updates sink past it                          */   \
+      asm volatile("" : "+v"(rdv));                                          \
+      row[t] = (i == t) ? dv : row[t] * rdv;                                 \
+      _Pragma("unroll") for (int j = t + 1; j < 16; ++j)                     \
+        row[j] = fma(-row[t], row_bcast(row[t], j), row[j]);                 \
+      /* one step at a time: hoisting later steps' broadcasts spills   */   \
+      __builtin_amdgcn_sched_barrier(0);                                     \
     }                                                                        \
     _Pragma("unroll") for (int c = 0; c < 16; ++c) if (c <= i)               \
         A_(dk0 + i, dk0 + c) = row[c];                                       \
     const int c = i;                                                         \
     double x[16];                                                            \
-    /* lane i computes only 1/L_ii; the rest arrive by shfl (16x less   */   \
-    /* serial f64 division work than every lane inverting all 16).      */   \
+    /* lane i computes only 1/L_ii; the rest arrive by broadcast (16x   */   \
+    /* less serial f64 division work than every lane inverting all 16). */   \
     /* predicated select avoids a dynamic register index (scratch!)     */   \
     /* the reciprocal broadcast is inlined per r (a diag[16] register   */   \
     /* array cost ~16 VGPR and a waves/SIMD tier)                       */   \
@@ -328,13 +370,14 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     _Pragma("unroll") for (int r = 0; r < 16; ++r) if (r == i) dii = row[r]; \
     const double myrcp = 1.0 / dii;                                          \
     _Pragma("unroll") for (int r = 0; r < 16; ++r) {                         \
-      const double dr = __shfl(myrcp, r, 16);                                \
+      const double dr = row_bcast(myrcp, r);                                 \
       double acc2 = 0.0;                                                     \
       _Pragma("unroll") for (int t = 0; t < 16; ++t) {                       \
-        const double lrt = __shfl(row[t], r, 16);                            \
-        if (t >= c && t < r) acc2 = fma(lrt, x[t], acc2);                    \
+        const double lrt = row_bcast(row[t], r);                             \
+        if (t < r) acc2 = fma(lrt, x[t], acc2);                              \
       }                                                                      \
       x[r] = (r < c) ? 0.0 : (r == c) ? dr : -acc2 * dr;                     \
+      __builtin_amdgcn_sched_barrier(0);                                     \
     }                                                                        \
     _Pragma("unroll") for (int r = 0; r < 16; ++r) (DST)[r][c] = x[r];       \
     if (lane < 16)                                                           \
@@ -367,7 +410,7 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     if (kb + 1 >= nb) break;
 
     // trailing phase A1: ONLY column kb+1 tiles, so its diagonal can
-    // factor next (all 8 waves)
+    // factor next (all waves)
     const int j1 = (kb + 1) * NB;
     for (int ib = kb + 1 + wv; ib < nb; ib += nwv) {
       const int i0 = ib * NB;
@@ -393,8 +436,9 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     // phase A2: wave 0 factors diagonal kb+1 while the other waves do
     // the remaining trailing tiles (jb >= kb+2).  (Rotating the factor
     // wave across kb to spread the serial phase over SIMDs was
-    // measured NEUTRAL — the kernel's parking is not SIMD-0 contention
-    // — and was reverted.)
+    // measured neutral with the LDS-permute chain and neutral to 1.5%
+    // slower with the DPP chain — docs/TUNING_NOTES.md — and is not
+    // built.)
     if (wv == 0) {
       CHOL_DIAG(kb + 1, inv16[(kb + 1) & 1]);
     } else {
@@ -423,6 +467,7 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     }
     __syncthreads();
   }
+#undef CHOL_DIAG
 
   // write back L (full rows; the upper triangle is never read and
   // gets deterministic zeros)
@@ -1264,8 +1309,10 @@ int launch_sbgemm(const double* T, const double* toas, const double* ninv,
 int launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
                       int D, int P, double* L, double* invd,
                       hipStream_t stream) {
-  // small matrices: 256 threads -> 4 workgroups/CU despite the 115-VGPR
-  // diagonal-factor pressure; large: 512 threads for MFMA coverage
+  // small matrices: 256 threads, so that 5 workgroups per CU (the
+  // ~95-VGPR diagonal factor allows 5 waves/SIMD) run their serial
+  // chains side by side (128 threads, 7 per CU by LDS: within noise,
+  // docs/TUNING_NOTES.md); large: 512 threads for MFMA coverage
   const dim3 grid(D, P), blk(mp <= 64 ? 256 : 512);
   switch (mp >> 4) {
 #define CHOL_CASE(NBT) \

@@ -25,7 +25,7 @@ def init_distributed(backend: str = None, device: torch.device = None):
     Returns (rank, world_size, device).  With no RANK in the env this is
     a single-process run: returns (0, 1, device) without init.
     Backend default: "nccl" (= RCCL on ROCm) when CUDA devices are
-    visible, else "gloo".
+    visible and ``device`` is not a CPU device, else "gloo".
 
     A torchrun launch with WORLD_SIZE=1 still initializes the process
     group: the RCCL communicator setup and every collective call site
@@ -41,7 +41,11 @@ def init_distributed(backend: str = None, device: torch.device = None):
     world = int(os.environ["WORLD_SIZE"])
     local_rank = int(os.environ.get("LOCAL_RANK", rank))
     if backend is None:
-        backend = "nccl" if torch.cuda.is_available() else "gloo"
+        # an explicit CPU device keeps gloo on a box that has GPUs: nccl
+        # has no collectives for CPU tensors
+        on_cpu = device is not None and torch.device(device).type == "cpu"
+        backend = ("nccl" if torch.cuda.is_available() and not on_cpu
+                   else "gloo")
     if device is None:
         if torch.cuda.is_available():
             torch.cuda.set_device(local_rank)

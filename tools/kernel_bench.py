@@ -10,6 +10,11 @@ Prints per-kernel wall time and fp64 TFLOP/s at the NMFp bench shape.
 times the two solve kernels of the stacked compressed sweep
 (trsm_fp_accum, trsm_fp_store); defaults P=67, D=1024, F=1000, m=60.
 
+    python tools/kernel_bench.py factor [P D m]
+
+times the factor kernel alone (chol_batch_into) at the stacked shape;
+defaults P=67, D=1024, m=60 (mp = 64).
+
 times the Fe-on-device kernels (trsm_prods, fe_assemble, fe_skymax);
 defaults P=67, D=256, F=200, nsky=768, m=120.
 """
@@ -136,6 +141,31 @@ def main_stacked(P=67, D=1024, F=1000, m=60):
           f"  {flops/t/1e12:6.2f} TF/s")
 
 
+def main_factor(P=67, D=1024, m=60):
+    """The factor of one stacked draw chunk, isolated (67 pulsars, 1024
+    draws, mp = 64): chol_batch_into caller-owned buffers, as the
+    sweep's pipeline calls it.  Device events.  In the step this kernel
+    runs beside the solve on a side stream and costs the step about 0.8
+    of this figure (docs/TUNING_NOTES.md)."""
+    mp = (m + 15) // 16 * 16
+    ntoa = 2000
+    rng = np.random.default_rng(0)
+    T = torch.as_tensor(rng.normal(size=(P, ntoa, m)), dtype=torch.float64,
+                        device=DEV)
+    TNT = (T.transpose(1, 2) @ T * 1e12).contiguous()  # (P, m, m)
+    del T
+    phiinv = torch.as_tensor(rng.uniform(0.5, 2.0, (P, D, m)) * 1e10,
+                             dtype=torch.float64, device=DEV)
+    L = torch.empty((P * D, mp, mp), dtype=torch.float64, device=DEV)
+    invd = torch.empty((P * D, mp // 16, 16, 16), dtype=torch.float64,
+                       device=DEV)
+    t = timeit(lambda: ext.chol_batch_into(TNT, phiinv, mp, L, invd),
+               iters=50, warmup=5)
+    print(f"chol_batch_into P={P} D={D} mp={mp}: {t*1e3:9.3f} ms"
+          f"  ({t/(P*D)*1e9:7.1f} ns/matrix,"
+          f" {P*D*(mp*mp+mp*16)*8/t/1e9:7.1f} GB/s written)")
+
+
 def main_fe(P=67, D=256, F=200, nsky=768, m=120):
     """Fe on device: products mode of the solve + the two sky kernels.
 
@@ -191,6 +221,8 @@ def main_fe(P=67, D=256, F=200, nsky=768, m=120):
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "fe":
         main_fe(*[int(a) for a in sys.argv[2:]])
+    elif len(sys.argv) > 1 and sys.argv[1] == "factor":
+        main_factor(*[int(a) for a in sys.argv[2:]])
     elif len(sys.argv) > 1 and sys.argv[1] == "stacked":
         main_stacked(*[int(a) for a in sys.argv[2:]])
     else:
