@@ -75,7 +75,14 @@ class SolveSystem(NamedTuple):
 
     The same description serves one pulsar (``A`` (m, m), ``var`` a
     slice) and the pulsar stack (``A`` (P, m, m), ``var`` one slice per
-    pulsar)."""
+    pulsar).
+
+    ``lead`` (stacked compressed system only): ``A`` and ``RHS`` carry
+    the padding of the solve dimension to a multiple of 16 themselves,
+    in FRONT — ``A = blockdiag(I_lead, G)``, ``lead`` zero rows on top
+    of ``RHS`` — and ``diag`` left-pads with zeros, so the padded Sigma
+    has an exact identity block.  ``var`` and ``delta0`` keep the
+    unpadded dimension."""
 
     A: torch.Tensor
     RHS: torch.Tensor
@@ -84,13 +91,17 @@ class SolveSystem(NamedTuple):
     gsign: float
     var: object = slice(None)  # columns of phiinv the diagonal is built from
     delta0: torch.Tensor = None  # compressed only: the reference prior
+    lead: int = 0  # leading identity rows of A (zero rows of RHS)
 
     def diag(self, pinv):
         """phiinv rows (..., D, m), already cut to ``var``, -> the
         diagonal added to ``A``."""
         if self.delta0 is None:
             return pinv
-        return 1.0 / (pinv - self.delta0[..., None, :])
+        d = 1.0 / (pinv - self.delta0[..., None, :])
+        if self.lead:
+            d = torch.nn.functional.pad(d, (self.lead, 0))
+        return d
 
 
 def _close_2x2(prods, fp_out):
@@ -454,11 +465,28 @@ class FpEngine:
             torch.stack(ts).contiguous()
             for ts in zip(*(s[:4] for s in systems))
         )
-        delta0 = None
+        delta0, lead = None, 0
         if systems[0].delta0 is not None:
             delta0 = torch.stack([s.delta0 for s in systems]).contiguous()
+            # Compressed stack within the draw-looping solve: pad the
+            # solve dimension in FRONT.  Sigma then starts with an exact
+            # identity block over zero RHS rows, L[lead:, :lead] and the
+            # first `lead` rows of W are exact zeros, and trsm_fp_store
+            # leaves out the MFMAs that would multiply them.
+            mv = A.shape[-1]
+            mp = ops.pad16(mv)
+            if mp <= self.DRAW_LOOP_MAX_MP and mp > mv:
+                lead = mp - mv
+                Ap = A.new_zeros((A.shape[0], mp, mp))
+                Ap[:, :lead, :lead] = torch.eye(lead, dtype=A.dtype,
+                                                device=A.device)
+                Ap[:, lead:, lead:] = A
+                Kp = RHS.new_zeros((RHS.shape[0], mp, RHS.shape[2]))
+                Kp[:, lead:] = RHS[:, :mv]
+                A, RHS = Ap, Kp
         return SolveSystem(A, RHS, S, R, systems[0].gsign,
-                           var=[s.var for s in systems], delta0=delta0)
+                           var=[s.var for s in systems], delta0=delta0,
+                           lead=lead)
 
     def _stack_direct(self):
         """Stacked DIRECT system (same dimensions across pulsars; used
@@ -738,6 +766,8 @@ class FpEngine:
         fp_pp = torch.empty((P, chunks[0][1], F), dtype=torch.float64,
                             device=self.device)
         mp = ops.pad16(st.A.shape[-1])
+        # the solve skips whole 4-row k-steps of the leading pad
+        skip = st.lead - st.lead % 4
         if len(chunks) > 1 and mp <= ops.MAX_MP_CHOL:
             # SOFTWARE PIPELINE across draw chunks: chunk k+1's factor
             # runs on a side stream beside chunk k's solve.  The solve
@@ -756,7 +786,7 @@ class FpEngine:
                 n = P * (hi - lo)
                 if self._draw_loop_solve(mp, hi - lo):
                     ext.trsm_fp_store(L[:n], invd[:n], st.RHS, st.S, st.R,
-                                      pp, st.gsign)
+                                      pp, st.gsign, lead=skip)
                 else:
                     pp.zero_()
                     ext.trsm_fp_accum(L[:n], invd[:n], st.RHS, st.S, st.R,
@@ -775,7 +805,8 @@ class FpEngine:
                                  device=self.device)
             if self._draw_loop_solve(mp, hi - lo):
                 L, invd = ext.chol_batch(st.A, d, mp)
-                ext.trsm_fp_store(L, invd, st.RHS, st.S, st.R, pp, st.gsign)
+                ext.trsm_fp_store(L, invd, st.RHS, st.S, st.R, pp, st.gsign,
+                                  lead=skip)
             else:
                 pp.zero_()
                 ops.chol_trsm_fp_accum(st.A, d, st.RHS, st.S, st.R, pp,

@@ -20,7 +20,7 @@ int launch_trsm_fp(const double*, const double*, const double*,
                    double, double*, hipStream_t);
 int launch_trsm_fp_draws(const double*, const double*, const double*,
                          const double*, const double*, int, int, int, int,
-                         double, double*, int, int, hipStream_t);
+                         double, double*, int, int, int, hipStream_t);
 int trsm_fp_draws_tile_freqs();
 int launch_sigdots_block(const double*, const double*, const double*,
                          const double*, const double*, const long*,
@@ -223,15 +223,21 @@ void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
 // the device's resident workgroup slots).  Plain stores: every entry of
 // `out` (D,F) / (P,D,F) is written and none is read, so `out` need not
 // be initialised; the values equal trsm_fp_accum into zeros bit for bit.
+// `lead` (0, 4, 8 or 12) promises that the first `lead` rows of RHS are
+// zero and that the system starts with a `lead` x `lead` identity block
+// (L[lead:, :lead] = 0): the kernel then leaves out the MFMAs that would
+// multiply those zeros, and the result keeps every bit of lead = 0.
 void trsm_fp_store(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                    torch::Tensor sNs, torch::Tensor sNr, torch::Tensor out,
-                   double gsign, int64_t draws_per_block) {
+                   double gsign, int64_t draws_per_block, int64_t lead) {
   const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, out, "out", 0);
   TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 64,
               "trsm_fp_store supports a padded solve dimension mp <= 64 "
               "(multiple of 16); got mp=", d.mp, " — use trsm_fp_accum");
   TORCH_CHECK(draws_per_block >= 0 && draws_per_block < (1L << 31),
               "draws_per_block must be >= 0");
+  TORCH_CHECK(lead >= 0 && lead <= 12 && lead % 4 == 0,
+              "lead must be 0, 4, 8 or 12; got ", lead);
   if (d.D == 0 || d.F == 0 || d.P == 0) return;
   // the factor is fetched with 16-byte loads
   TORCH_CHECK((reinterpret_cast<uintptr_t>(L.data_ptr<double>()) |
@@ -243,7 +249,7 @@ void trsm_fp_store(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                            RHS.data_ptr<double>(), sNs.data_ptr<double>(),
                            sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
                            out.data_ptr<double>(), (int)draws_per_block, ncu,
-                           stream()),
+                           (int)lead, stream()),
       "trsm_fp_store");
 }
 
@@ -388,7 +394,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "draw-looping TRSM + fused 2x2 Fp reduction, plain stores (mp <= 64)",
         py::arg("L"), py::arg("invd"), py::arg("RHS"), py::arg("sNs"),
         py::arg("sNr"), py::arg("out"), py::arg("gsign"),
-        py::arg("draws_per_block") = 0);
+        py::arg("draws_per_block") = 0, py::arg("lead") = 0);
   m.def("trsm_fp_store_tile_freqs", &trsm_fp_draws_tile_freqs,
         "frequencies per workgroup tile of trsm_fp_store");
   m.def("trsm_prods", &trsm_prods,

@@ -757,6 +757,16 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
 //     the w*u sum waits for the barrier that publishes the u column;
 //   * the partner column (lane ^ 1) comes by DPP, not by an LDS permute.
 //
+// SKIP (0..3) is the caller's promise that the first 4*SKIP rows of the
+// RHS are zero and that the system starts with an identity block of that
+// size (L[4*SKIP:, :4*SKIP] = 0), as the engine's compressed stack pads
+// m_v = 60 to 64 in FRONT.  W rows 0 .. 4*SKIP-1 are then exact zeros,
+// and for kk < SKIP the kernel leaves out the MFMA of every cb = 0
+// update and of row block 0's diagonal multiply: products with an exact
+// zero operand, so no bit changes against SKIP = 0 on the same system.
+// Every other MFMA and every fma keeps its order.  MFMAs per wave and
+// draw at NBT = 4: 40, 36, 32, 28 for SKIP 0..3 (NBT fewer per step).
+//
 // Grid: 1-D, 8 * ceil(P*nsl / 8) * ntile blocks, decoded as
 //   g = bid % 8, j = bid / 8, slice s = (j / ntile) * 8 + g,
 //   tile = j % ntile, pulsar = s / nsl, draws [(s % nsl) * dpb, +dpb)
@@ -772,10 +782,12 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
 //   2 x mp doubles: the solved u column, by draw parity;
 //   5 x 64 doubles: sNs/sNr of the tile's frequencies.
 // block = 512 (8 waves), tile = 63 frequencies + u as in trsm_fp_kernel.
-// Registers as compiled (gfx950, -O3): NBT=4 128 VGPR, 4 waves/SIMD
-// (two workgroups per CU; 8 bytes of spill, reloaded once per draw); NBT=3
-// 104, NBT=2 72, NBT=1 46.  RHS copy 8*NBT, W 8*NBT, the three
-// accumulators 24, the prefetched factor 4*NBT.
+// Registers as compiled (gfx950, -O3), SKIP = 0 / 1 / 2 / 3: NBT=4
+// 128 / 127 / 125 / 123 VGPR, 4 waves/SIMD (two workgroups per CU;
+// SKIP = 0 has 8 bytes of spill, reloaded once per draw, the others
+// none); NBT=3 104 / 95 / 100 / 98, NBT=2 72 / 71 / 69 / 67, NBT=1
+// 46 / 44 / 42 / 40.  RHS copy 8*NBT, W 8*NBT, the three accumulators
+// 24, the prefetched factor 4*NBT.  LDS is the same for every SKIP.
 // ---------------------------------------------------------------------
 #define DL_BS 18              // row stride of a staged block (doubles)
 #define DL_BLK (16 * DL_BS)   // doubles per staged block
@@ -791,7 +803,7 @@ static __device__ __forceinline__ double pair_swap(double w) {
   return __hiloint2double(hi, lo);
 }
 
-template <int NBT>
+template <int NBT, int SKIP>
 __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
     const double* __restrict__ L_all /*(P*D,mp,mp)*/,
     const double* __restrict__ invd_all /*(P*D, mp/16, 16, 16)*/,
@@ -930,6 +942,7 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
       for (int cb = 0; cb < rb; ++cb) {
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
+          if (cb == 0 && kk < SKIP) continue;  // W rows 4kk..4kk+3 are 0
           const double a =
               Sb[(rb * (rb - 1) / 2 + cb) * DL_BLK + kk * 4 + aoff];
           if (cb & 1)
@@ -942,6 +955,7 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
       f64x4 sol = f64x4{0, 0, 0, 0};
 #pragma unroll
       for (int kk = 0; kk < 4; ++kk) {
+        if (rb == 0 && kk < SKIP) continue;  // acc rows 4kk..4kk+3 are 0
         const double a = Sb[(NLB + rb) * DL_BLK + kk * 4 + aoff];
         sol = MFMA_F64(a, acc[kk], sol);
       }
@@ -1369,7 +1383,8 @@ int launch_trsm_fp_draws(const double* L, const double* invd,
                          const double* RHS, const double* sNs,
                          const double* sNr, int mp, int F, int D, int P,
                          double gsign, double* fp, int draws_per_block,
-                         int ncu, hipStream_t stream) {
+                         int ncu, int lead, hipStream_t stream) {
+  if (lead < 0 || lead > 12 || (lead & 3)) return (int)hipErrorInvalidValue;
   const int ntile = (F + DL_FREQS - 1) / DL_FREQS;
   int dpb = draws_per_block, nsl = 0;
   auto plan = [&](auto kern) -> long {
@@ -1390,17 +1405,21 @@ int launch_trsm_fp_draws(const double* L, const double* invd,
     nsl = (D + dpb - 1) / dpb;
     return ((long)P * nsl + 7) / 8 * 8 * ntile;
   };
-  switch (mp >> 4) {
-#define DRAWS_CASE(NBT) \
-    case NBT: { \
-      auto kern = trsm_fp_draws_kernel<NBT>; \
+  if (mp < 16 || mp > 64 || (mp & 15)) return (int)hipErrorInvalidValue;
+  switch ((mp >> 4) * 4 + (lead >> 2)) {
+#define DRAWS_CASE(NBT, SKIP) \
+    case NBT * 4 + SKIP: { \
+      auto kern = trsm_fp_draws_kernel<NBT, SKIP>; \
       const long nblk = plan(kern); \
       if (nblk >= (1L << 31)) return (int)hipErrorInvalidValue; \
       hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), 0, stream, \
                          L, invd, RHS, sNs, sNr, F, D, P, dpb, nsl, gsign, \
                          fp); \
     } break;
-    DRAWS_CASE(1) DRAWS_CASE(2) DRAWS_CASE(3) DRAWS_CASE(4)
+#define DRAWS_NBT(NBT) \
+    DRAWS_CASE(NBT, 0) DRAWS_CASE(NBT, 1) DRAWS_CASE(NBT, 2) DRAWS_CASE(NBT, 3)
+    DRAWS_NBT(1) DRAWS_NBT(2) DRAWS_NBT(3) DRAWS_NBT(4)
+#undef DRAWS_NBT
 #undef DRAWS_CASE
     default: return (int)hipErrorInvalidValue;
   }

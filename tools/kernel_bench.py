@@ -9,6 +9,8 @@ Prints per-kernel wall time and fp64 TFLOP/s at the NMFp bench shape.
 
 times the two solve kernels of the stacked compressed sweep
 (trsm_fp_accum, trsm_fp_store); defaults P=67, D=1024, F=1000, m=60.
+Where m is short of mp by 4 or more it also times trsm_fp_store on the
+same system padded in front, with lead = 0 and with the skipped k-steps.
 
     python tools/kernel_bench.py factor [P D m]
 
@@ -139,6 +141,30 @@ def main_stacked(P=67, D=1024, F=1000, m=60):
                iters=iters)
     print(f"trsm_fp_store P={P} D={D} F={F} mp={mp}: {t*1e3:9.3f} ms"
           f"  {flops/t/1e12:6.2f} TF/s")
+
+    # lead arm: the same system with the pad in FRONT (identity block,
+    # zero RHS rows on top, as the engine's compressed stack presents
+    # it), solved with and without the skipped k-steps
+    lead = mp - m
+    skip = lead - lead % 4
+    if skip == 0:
+        return
+    A = torch.zeros((P, mp, mp), dtype=torch.float64, device=DEV)
+    A[:, :lead, :lead] = torch.eye(lead, dtype=torch.float64, device=DEV)
+    A[:, lead:, lead:] = TNT
+    pad = torch.nn.functional.pad(phiinv, (lead, 0))
+    RHSl = torch.zeros_like(RHS)
+    RHSl[:, lead:] = RHS[:, :m]
+    L, invd = ext.chol_batch(A, pad, mp)
+    ref = torch.full_like(out, float("nan"))
+    ext.trsm_fp_store(L, invd, RHSl, sNs, sNr, ref, -1.0, lead=0)
+    ext.trsm_fp_store(L, invd, RHSl, sNs, sNr, out, -1.0, lead=skip)
+    assert torch.equal(ref, out), "trsm_fp_store lead != lead=0"
+    for ld in (0, skip):
+        t = timeit(lambda: ext.trsm_fp_store(L, invd, RHSl, sNs, sNr, out,
+                                             -1.0, lead=ld), iters=iters)
+        print(f"trsm_fp_store P={P} D={D} F={F} mp={mp} front pad, lead={ld}:"
+              f" {t*1e3:9.3f} ms  {flops/t/1e12:6.2f} TF/s")
 
 
 def main_factor(P=67, D=1024, m=60):

@@ -34,6 +34,11 @@ if any('pmc_event' in n for n in names):
         mf = v.get('SQ_VALU_MFMA_BUSY_CYCLES', 0) / (wc * 4)
         if 'SQ_WAVE_CYCLES' in v:
             print(f"{k:36s} waitANY={wa:5.1%} waitINST={wi:5.1%} mfmaBusy={mf:5.1%}")
+            # absolute counts per dispatch: a kernel that gets shorter
+            # can keep its ratios
+            print(f"{k:36s} waveCycles={wc:.4g} "
+                  f"mfmaBusyCycles={v.get('SQ_VALU_MFMA_BUSY_CYCLES', 0):.4g}"
+                  " per dispatch")
         # memory side, per dispatch (averages): L2 hit rate and the
         # bytes the L2 fetched from beyond it (FETCH_SIZE is in KiB)
         hit = v.get('TCC_HIT_sum', v.get('TCC_HIT'))
