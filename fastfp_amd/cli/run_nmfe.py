@@ -12,6 +12,8 @@ columns stripped); the sky grid mirrors ``run_fe``.  Output:
 ``{savefile}.max.npy`` (nsamples, nfreqs) and ``{savefile}.argmax.npy``
 (indices into the meta JSON's ``sky`` list).  ``--assemble device``
 runs the sky assembly of the cube in the HIP kernel (GPU only).
+``--compress`` takes the per-pulsar products from the Schur-compressed
+per-draw systems, as ``run_nmfp`` does for Fp.
 """
 
 import argparse
@@ -55,6 +57,7 @@ def main(
     batch_size=64,
     skymax=False,
     assemble="host",
+    compress=False,
 ):
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.INFO)
     logger = logging.getLogger(__name__)
@@ -110,6 +113,13 @@ def main(
     if len(my_idx):
         engine = FpEngine(psrs, Nvecs, Ts, device=dev)
         engine.precompute(freqs)
+        if compress:
+            # Schur draw compression: per-draw solves run at the
+            # variable-bin dimension only (docs/DESIGN.md)
+            engine.enable_draw_compression(
+                [c.var_slice for c in pta.rn_containers],
+                [c.get_phiinv(noise) for c in pta.rn_containers],
+            )
     parts, parts_arg = [], []
     for lo in range(0, len(my_idx), batch_size):
         sel = my_idx[lo : lo + batch_size]
@@ -118,12 +128,14 @@ def main(
         }
         if skymax:
             fm, am = nm.sweep_max(freqs, sky, samples, Nvecs, Ts,
-                                  device=dev, engine=engine)
+                                  device=dev, engine=engine,
+                                  compress=compress)
             parts.append(fm)
             parts_arg.append(am)
         else:
             parts.append(nm.sweep(freqs, sky, samples, Nvecs, Ts, device=dev,
-                                  engine=engine, assemble=assemble))
+                                  engine=engine, assemble=assemble,
+                                  compress=compress))
     tail = (ncwfreqs,) if skymax else (len(sky), ncwfreqs)
     local = np.concatenate(parts, axis=0) if parts else np.zeros((0,) + tail)
     t_local = torch.as_tensor(local, dtype=torch.float64)
@@ -181,6 +193,10 @@ def cli():
     parser.add_argument("--assemble", choices=["host", "device"],
                         default="host",
                         help="where the sky assembly of the cube runs")
+    parser.add_argument("--compress", action="store_true",
+                        help="solve the Schur-compressed per-draw systems "
+                             "(variable prior bins only), draw by draw where "
+                             "the compression margin allows")
     main(**vars(parser.parse_args()))
 
 

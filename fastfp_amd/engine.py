@@ -813,7 +813,8 @@ class FpEngine:
                                        gsign=st.gsign)
             fp[lo:hi] += pp.sum(dim=0)
 
-    def sweep_products(self, sigmas=None, phiinvs=None) -> torch.Tensor:
+    def sweep_products(self, sigmas=None, phiinvs=None,
+                       compressed: bool = False) -> torch.Tensor:
         """Per-pulsar corrected inner products
         [s|s, c|c, s|c, s|r, c|r], each ``(x|y) = x^T C_p^{-1} y``
         over the precomputed frequency grid.
@@ -828,26 +829,47 @@ class FpEngine:
         reuse the engine's precompute + one m-dim solve per (pulsar,
         draw) and pay only O(P) per additional sky location.  Runs on
         the engine's device (torch batched Cholesky/solve — setup-
-        scale work, not the draw-batched Fp hot path)."""
+        scale work, not the draw-batched Fp hot path).
+
+        ``compressed`` (``phiinvs`` only): take each pulsar's products
+        from its Schur-compressed system where it has one
+        (:meth:`enable_draw_compression`), from the direct system
+        otherwise.  The per-draw margin is the caller's business, as in
+        :meth:`sweep`."""
         assert self.freqs is not None, "call precompute(freqs) first"
+        if compressed and sigmas is not None:
+            raise ValueError("compressed=True takes phiinvs, not sigmas")
         if sigmas is not None:
             dense = [_t64(s, self.device) for s in sigmas]
             batched = dense[0].dim() == 3
             dense = [s[None] if s.dim() == 2 else s for s in dense]
+            systems = [blk.direct for blk in self.blocks]
         else:
             rows, batched = self._rows(phiinvs)
-            dense = [blk.TNT[None] + torch.diag_embed(p)
-                     for blk, p in zip(self.blocks, rows)]
+            systems = [
+                blk.comp if compressed and blk.comp is not None
+                else blk.direct
+                for blk in self.blocks
+            ]
+            dense = [self._dense(sy, p) for sy, p in zip(systems, rows)]
         out = torch.stack([
-            torch.stack(_eager_products(blk.direct, sigma), dim=1)
-            for blk, sigma in zip(self.blocks, dense)
+            torch.stack(_eager_products(sy, sigma), dim=1)
+            for sy, sigma in zip(systems, dense)
         ])  # (P, D, 5, F)
         return out[:, 0] if not batched else out
 
-    def sweep_products_hip(self, phiinvs, draw_chunk: int = 32) -> torch.Tensor:
+    @staticmethod
+    def _dense(system: SolveSystem, pinv):
+        """(D, m, m) ``A + diag(d)`` of one pulsar's system for the
+        (D, m) phiinv rows ``pinv``."""
+        return system.A[None] + torch.diag_embed(
+            system.diag(pinv[:, system.var]))
+
+    def sweep_products_hip(self, phiinvs, draw_chunk: int = 32,
+                           compressed: bool = False) -> torch.Tensor:
         """:meth:`sweep_products` on the HIP solve: the same five
         corrected products, stored un-collapsed by the products mode of
-        the trsm kernel.
+        the trsm kernels.
 
         ``phiinvs``: per-pulsar (m,) or (D, m) diagonal phi^-1; returns
         the (P, 5, F) / (P, D, 5, F) device tensor.  When every pulsar
@@ -855,14 +877,44 @@ class FpEngine:
         ``chol_batch`` and ONE ``trsm_prods`` launch per draw chunk
         across all pulsars, on the direct (uncompressed) system.
         Otherwise (CPU/eager engine, ragged bases, larger m) it returns
-        ``self.sweep_products(phiinvs=...)``."""
+        ``self.sweep_products(phiinvs=...)``.
+
+        ``compressed``: solve the Schur-compressed systems instead
+        (:meth:`enable_draw_compression`), at the variable dimension:
+
+        * stacked compression: one ``chol_batch`` per draw chunk on the
+          stacked system, then ``trsm_prods_store`` (the draw-looping
+          kernel) where :meth:`_draw_loop_solve` holds and
+          ``trsm_prods`` on the same padded system otherwise;
+        * no stack (ragged variable dimensions, or pulsars that lost
+          compression): per pulsar, its compressed system where it has
+          one and its direct system otherwise, on the HIP kernels while
+          that system's padded dimension is within ``MAX_MP_CHOL`` and
+          eager beyond;
+        * nothing compressed: the same as ``compressed=False``.
+
+        No limit on ``m`` and no common basis size is needed.  The
+        per-draw margin is the caller's business, as in :meth:`sweep`."""
         assert self.freqs is not None, "call precompute(freqs) first"
+        if compressed:
+            if not self._use_hip:
+                return self.sweep_products(phiinvs=phiinvs, compressed=True)
+            if any(blk.comp is not None for blk in self.blocks):
+                return self._products_compressed_hip(phiinvs, draw_chunk)
         st = self._direct_stack
         if st is None or ops.pad16(st.A.shape[-1]) > ops.MAX_MP_CHOL:
             return self.sweep_products(phiinvs=phiinvs)
+        rows, batched = self._rows(phiinvs)
+        out = self._products_stacked(st, rows, draw_chunk)
+        return out if batched else out[:, 0]
+
+    def _products_stacked(self, st: SolveSystem, rows, draw_chunk):
+        """(P, D, 5, F) products of a stacked system within
+        ``MAX_MP_CHOL``: one factor and one solve launch per draw
+        chunk."""
         ext = self._ext
         mp = ops.pad16(st.A.shape[-1])
-        rows, batched = self._rows(phiinvs)
+        skip = st.lead - st.lead % 4
         P, D, F = len(rows), rows[0].shape[0], self.freqs.shape[0]
         chunks, diag = self._stacked_chunks(st, rows, draw_chunk)
         out = torch.empty((P, D, 5, F), dtype=torch.float64,
@@ -872,7 +924,45 @@ class FpEngine:
             # a draw slice of `out` is not contiguous
             part = out if (lo, hi) == (0, D) else torch.empty(
                 (P, hi - lo, 5, F), dtype=torch.float64, device=self.device)
-            ext.trsm_prods(L, invd, st.RHS, st.S, st.R, part, st.gsign)
+            if st.delta0 is not None and self._draw_loop_solve(mp, hi - lo):
+                ext.trsm_prods_store(L, invd, st.RHS, st.S, st.R, part,
+                                     st.gsign, lead=skip)
+            else:
+                ext.trsm_prods(L, invd, st.RHS, st.S, st.R, part, st.gsign)
             if part is not out:
                 out[:, lo:hi] = part
+        return out
+
+    def _products_compressed_hip(self, phiinvs, draw_chunk):
+        """``sweep_products_hip(compressed=True)`` on a HIP engine with
+        at least one compressed pulsar."""
+        rows, batched = self._rows(phiinvs)
+        st = self._comp_stack
+        if st is not None:
+            if ops.pad16(st.A.shape[-1]) > ops.MAX_MP_CHOL:
+                return self.sweep_products(phiinvs=phiinvs, compressed=True)
+            out = self._products_stacked(st, rows, draw_chunk)
+            return out if batched else out[:, 0]
+        ext = self._ext
+        D, F = rows[0].shape[0], self.freqs.shape[0]
+        out = torch.empty((len(rows), D, 5, F), dtype=torch.float64,
+                          device=self.device)
+        for i, (blk, p) in enumerate(zip(self.blocks, rows)):
+            sy = blk.comp if blk.comp is not None else blk.direct
+            mp = ops.pad16(sy.A.shape[-1])
+            if mp > ops.MAX_MP_CHOL:
+                out[i] = torch.stack(
+                    _eager_products(sy, self._dense(sy, p)), dim=1)
+                continue
+            for lo in range(0, D, draw_chunk):
+                hi = min(lo + draw_chunk, D)
+                d = sy.diag(p[lo:hi, sy.var]).contiguous()
+                L, invd = ext.chol_batch(sy.A, d, mp)
+                part = out[i, lo:hi]  # (Dc, 5, F), contiguous
+                if self._draw_loop_solve(mp, hi - lo):
+                    ext.trsm_prods_store(L, invd, sy.RHS, sy.S, sy.R, part,
+                                         sy.gsign)
+                else:
+                    ext.trsm_prods(L, invd, sy.RHS, sy.S, sy.R, part,
+                                   sy.gsign)
         return out if batched else out[:, 0]

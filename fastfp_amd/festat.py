@@ -353,6 +353,57 @@ class NMFe:
         self.rn_sigs = rn_sigs
         self.fe = FastFe(psrs)  # validates .pos, holds antenna inputs
 
+    def _engine(self, engine, freqs, samples, Nvecs, Ts, device, compress,
+                freq_chunk=2048):
+        """The caller's engine, or a fresh one on ``device`` — with draw
+        compression enabled around the first draw when ``compress``."""
+        if engine is not None:
+            return engine
+        engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
+        engine.precompute(freqs, freq_chunk=freq_chunk)
+        if compress:
+            # fixed phi^-1 from any parameter point; variable bins are
+            # zeroed inside enable_draw_compression
+            probe = {k: (v[0] if np.ndim(v) else v)
+                     for k, v in samples.items()}
+            engine.enable_draw_compression(
+                [sig.var_slice for sig in self.rn_sigs],
+                [sig.get_phiinv(probe) for sig in self.rn_sigs],
+            )
+        return engine
+
+    @staticmethod
+    def _products(engine, chunk, compress: bool, hip: bool):
+        """(P, Dc, 5, F) products of one draw chunk, on the HIP solve
+        (``hip``) or the eager one.  With ``compress``, the per-draw
+        guard of ``NMFp.sweep``: draws whose compression margin is at
+        least 1.5 go through the compressed systems, the (rare)
+        prior-corner draws through the exact direct ones, and the rows
+        are scattered back in order."""
+        if hip:
+            run = engine.sweep_products_hip
+        else:
+            def run(p, **kw):
+                return engine.sweep_products(phiinvs=p, **kw)
+        if not (compress and any(b.comp is not None for b in engine.blocks)):
+            return run(chunk)
+        # one copy to the engine's device serves the margin and the solve
+        chunk = [p.to(engine.device) for p in chunk]
+        bad = engine.compression_margin_per_draw(chunk) < 1.5
+        if not bool(bad.any()):
+            return run(chunk, compressed=True)
+        out = None
+        for idx, comp in ((torch.nonzero(~bad).reshape(-1), True),
+                          (torch.nonzero(bad).reshape(-1), False)):
+            if not len(idx):
+                continue
+            part = run([p[idx.to(p.device)] for p in chunk], compressed=comp)
+            if out is None:
+                out = part.new_empty((part.shape[0], bad.shape[0])
+                                     + tuple(part.shape[2:]))
+            out[:, idx.to(out.device)] = part
+        return out
+
     def sweep(
         self,
         freqs,
@@ -365,6 +416,7 @@ class NMFe:
         freq_chunk: int = 2048,
         engine: FpEngine = None,
         assemble: str = "host",
+        compress: bool = False,
     ) -> np.ndarray:
         """Fe over (draws x sky x freqs).  ``samples``: parameter-name
         -> (D,) arrays (the ``map_params`` format).  Returns
@@ -373,13 +425,17 @@ class NMFe:
         ``assemble="device"`` (HIP engines only): products from the HIP
         solve, sky assembly in the ``fe_assemble`` kernel; only the
         finished map is copied to the host.  The default ``"host"`` is
-        the numpy assembly."""
+        the numpy assembly.
+
+        ``compress``: take the products from the Schur-compressed
+        per-draw systems (``NMFp.sweep``'s ``compress``), draw by draw
+        where the compression margin allows.  An engine built here gets
+        compression enabled; a caller's engine is used as it is."""
         from fastfp_amd.noise import batch_phiinv
 
         device = _check_assemble(assemble, device, engine)
-        if engine is None:
-            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
-            engine.precompute(freqs, freq_chunk=freq_chunk)
+        engine = self._engine(engine, freqs, samples, Nvecs, Ts, device,
+                              compress, freq_chunk)
         phiinvs = batch_phiinv(self.rn_sigs, samples)
         phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
         D = phiinvs[0].shape[0]
@@ -392,16 +448,17 @@ class NMFe:
             out = np.empty((D, len(sky), F))
             for lo in range(0, D, draw_chunk):
                 hi = min(lo + draw_chunk, D)
-                prods = engine.sweep_products_hip(
-                    [p[lo:hi] for p in phiinvs])  # (P, Dc, 5, F)
+                prods = self._products(
+                    engine, [p[lo:hi] for p in phiinvs], compress,
+                    hip=True)  # (P, Dc, 5, F)
                 out[lo:hi] = ops.fe_assemble(prods, ant_d).cpu().numpy()
             return out
         ant = [gw_antenna_pattern(self.fe.pos, th, ph) for th, ph in sky]
         out = np.empty((D, len(sky), F))
         for lo in range(0, D, draw_chunk):
             hi = min(lo + draw_chunk, D)
-            prods = engine.sweep_products(
-                phiinvs=[p[lo:hi] for p in phiinvs]
+            prods = self._products(
+                engine, [p[lo:hi] for p in phiinvs], compress, hip=False
             ).cpu().numpy()  # (P, Dc, 5, F)
             for k, (fplus, fcross) in enumerate(ant):
                 out[lo:hi, k, :] = _assemble_fe_draws(prods, fplus, fcross)
@@ -417,6 +474,7 @@ class NMFe:
         device: str = None,
         draw_chunk: int = 128,
         engine: FpEngine = None,
+        compress: bool = False,
     ):
         """Fe maximised over ``sky`` for every (draw, frequency).
 
@@ -426,15 +484,14 @@ class NMFe:
         ``fe_skymax`` kernel and only (Dc, F)-sized results leave the
         device; on a CPU engine each chunk is assembled on the host and
         reduced with ``np.nanmax`` / ``np.nanargmax`` (the reference
-        implementation).
+        implementation).  ``compress``: as in :meth:`sweep`.
         """
         from fastfp_amd.noise import batch_phiinv
 
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
-        if engine is None:
-            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
-            engine.precompute(freqs)
+        engine = self._engine(engine, freqs, samples, Nvecs, Ts, device,
+                              compress)
         phiinvs = batch_phiinv(self.rn_sigs, samples)
         phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
         D = phiinvs[0].shape[0]
@@ -451,12 +508,14 @@ class NMFe:
             hi = min(lo + draw_chunk, D)
             chunk = [p[lo:hi] for p in phiinvs]
             if engine._use_hip:
-                prods = engine.sweep_products_hip(chunk)  # (P, Dc, 5, F)
+                prods = self._products(engine, chunk, compress,
+                                       hip=True)  # (P, Dc, 5, F)
                 fm, am, _ = ops.fe_skymax(prods, ant_d)
                 femax[lo:hi] = fm.cpu().numpy()
                 argmax[lo:hi] = am.cpu().numpy()
             else:
-                prods = engine.sweep_products(phiinvs=chunk).cpu().numpy()
+                prods = self._products(engine, chunk, compress,
+                                       hip=False).cpu().numpy()
                 cube = np.stack([
                     _assemble_fe_draws(prods, ant[k, :, 0], ant[k, :, 1])
                     for k in range(len(sky))

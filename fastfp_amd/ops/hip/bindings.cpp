@@ -21,6 +21,9 @@ int launch_trsm_fp(const double*, const double*, const double*,
 int launch_trsm_fp_draws(const double*, const double*, const double*,
                          const double*, const double*, int, int, int, int,
                          double, double*, int, int, int, hipStream_t);
+int launch_trsm_prods_draws(const double*, const double*, const double*,
+                            const double*, const double*, int, int, int, int,
+                            double, double*, int, int, int, hipStream_t);
 int trsm_fp_draws_tile_freqs();
 int launch_sigdots_block(const double*, const double*, const double*,
                          const double*, const double*, const long*,
@@ -159,7 +162,7 @@ struct SolveDims {
   int P, mp, F, D;
 };
 
-// Shapes of one solve, shared by trsm_fp_accum and trsm_prods: single
+// Shapes of one solve, shared by the trsm_fp_* and trsm_prods* ops: single
 // pulsar (L (D,mp,mp), RHS (mp,2F+1), sNs (3,F), sNr (2,F)) or
 // pulsar-batched (L (P*D,mp,mp), RHS (P,mp,2F+1), sNs (P,3,F),
 // sNr (P,2,F)).  `out` is (D,[K,]F) / (P,D,[K,]F); K = 0 means no such
@@ -272,6 +275,37 @@ void trsm_prods(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                         sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
                         out.data_ptr<double>(), stream()),
       "trsm_prods");
+}
+
+// trsm_prods_store: the five products of trsm_prods for mp <= 64, by the
+// products mode of the draw-looping kernel (see trsm_fp_store for
+// `draws_per_block` and `lead`).  Plain stores: every entry of `out`
+// (D,5,F) / (P,D,5,F) is written and none is read; the values equal
+// trsm_prods on the same L/invd/RHS bit for bit.
+void trsm_prods_store(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
+                      torch::Tensor sNs, torch::Tensor sNr, torch::Tensor out,
+                      double gsign, int64_t draws_per_block, int64_t lead) {
+  const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, out, "out", 5);
+  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 64,
+              "trsm_prods_store supports a padded solve dimension mp <= 64 "
+              "(multiple of 16); got mp=", d.mp, " — use trsm_prods");
+  TORCH_CHECK(draws_per_block >= 0 && draws_per_block < (1L << 31),
+              "draws_per_block must be >= 0");
+  TORCH_CHECK(lead >= 0 && lead <= 12 && lead % 4 == 0,
+              "lead must be 0, 4, 8 or 12; got ", lead);
+  if (d.D == 0 || d.F == 0 || d.P == 0) return;
+  // the factor is fetched with 16-byte loads
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(L.data_ptr<double>()) |
+               reinterpret_cast<uintptr_t>(invd.data_ptr<double>())) % 16 == 0,
+              "L and invd must be 16-byte aligned");
+  const int ncu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  check_launch(
+      launch_trsm_prods_draws(L.data_ptr<double>(), invd.data_ptr<double>(),
+                              RHS.data_ptr<double>(), sNs.data_ptr<double>(),
+                              sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P,
+                              gsign, out.data_ptr<double>(),
+                              (int)draws_per_block, ncu, (int)lead, stream()),
+      "trsm_prods_store");
 }
 
 namespace {
@@ -399,6 +433,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "frequencies per workgroup tile of trsm_fp_store");
   m.def("trsm_prods", &trsm_prods,
         "batched TRSM storing the five corrected products (Fe input)");
+  m.def("trsm_prods_store", &trsm_prods_store,
+        "draw-looping TRSM storing the five corrected products (mp <= 64)",
+        py::arg("L"), py::arg("invd"), py::arg("RHS"), py::arg("sNs"),
+        py::arg("sNr"), py::arg("out"), py::arg("gsign"),
+        py::arg("draws_per_block") = 0, py::arg("lead") = 0);
   m.def("fe_assemble", &fe_assemble,
         "Fe sky assembly: MFMA pulsar sums + in-register 4x4 solve");
   m.def("fe_skymax", &fe_skymax,

@@ -30,7 +30,9 @@
 //   trsm_fp_draws_kernel — the same solve for mp <= 64 with the loop
 //                        over draws inside the workgroup: the RHS tile
 //                        stays on chip over a slice of draws, Fp is a
-//                        plain store (the stacked compressed sweep)
+//                        plain store (the stacked compressed sweep); its
+//                        products mode stores the five products (the
+//                        compressed Fe input)
 //   trsm_fp_rl_kernel  — right-looking form of the same solve, the
 //                        path for 128 < mp <= 256
 //   diag_inv_kernel    — inverted 16x16 diagonal blocks of a rocSOLVER
@@ -788,6 +790,18 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
 // none); NBT=3 104 / 95 / 100 / 98, NBT=2 72 / 71 / 69 / 67, NBT=1
 // 46 / 44 / 42 / 40.  RHS copy 8*NBT, W 8*NBT, the three accumulators
 // 24, the prefetched factor 4*NBT.  LDS is the same for every SKIP.
+//
+// PRODS: products mode (Fe), as trsm_fp_kernel's — the closing lane
+// stores the five corrected products into out[((p*D + d)*5 + i)*F + f]
+// (plain vector stores, every entry written, none read) instead of
+// closing them to Fp.  Solve, staging and the three sums are shared, so
+// the values equal trsm_fp_kernel<NBT, 1, true>'s bit for bit at every
+// SKIP.  As compiled, all 16 PRODS instantiations have the VGPR count,
+// spill (8 bytes at NBT=4 SKIP=0 only) and LDS of the Fp instantiation
+// with the same NBT and SKIP in the table above; SGPRs are 44 / 50 / 52 /
+// 54 at NBT 1..4 (43 at NBT=1 SKIP=3) against 44 / 50 / 50 / 50 (43).
+// The PRODS = false instantiations compile to the same instructions as
+// before the mode existed.
 // ---------------------------------------------------------------------
 #define DL_BS 18              // row stride of a staged block (doubles)
 #define DL_BLK (16 * DL_BS)   // doubles per staged block
@@ -803,7 +817,7 @@ static __device__ __forceinline__ double pair_swap(double w) {
   return __hiloint2double(hi, lo);
 }
 
-template <int NBT, int SKIP>
+template <int NBT, int SKIP, bool PRODS = false>
 __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
     const double* __restrict__ L_all /*(P*D,mp,mp)*/,
     const double* __restrict__ invd_all /*(P*D, mp/16, 16, 16)*/,
@@ -811,7 +825,8 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
     const double* __restrict__ sNs_all /*(P,3,F)*/,
     const double* __restrict__ sNr_all /*(P,2,F)*/, int F, int D, int P,
     int dpb /*draws per block*/, int nsl /*slices = ceil(D/dpb)*/,
-    double gsign, double* __restrict__ fp_all /*(P,D,F)*/) {
+    double gsign,
+    double* __restrict__ fp_all /*(P,D,F); PRODS: (P,D,5,F)*/) {
   constexpr int mp = NBT * 16;
   constexpr int UC = 126;  // block column of u
   constexpr int NLB = NBT * (NBT - 1) / 2;  // strict-lower blocks
@@ -993,10 +1008,23 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
     a3 += __shfl_down(a3, 32, 64); a3 += __shfl_down(a3, 16, 64);
     const double b1 = pair_swap(a1);  // cc (for even lanes)
     const double b2 = pair_swap(a2);  // cu
-    if (closer)
-      fp[(long)d * F + f] =
-          fp_close(Sc[q], Sc[64 + q], Sc[128 + q], Sc[192 + q], Sc[256 + q],
-                   gsign, a1, b1, a3, a2, b2);
+    if constexpr (PRODS) {
+      // the five corrected products of trsm_fp_kernel<.., true>, same
+      // expressions in the same order
+      if (closer) {
+        double* o = fp_all + (((long)pp * D + d) * 5) * F + f;
+        o[0] = Sc[q] - gsign * a1;
+        o[F] = Sc[64 + q] - gsign * b1;
+        o[2L * F] = Sc[128 + q] - gsign * a3;
+        o[3L * F] = Sc[192 + q] - gsign * a2;
+        o[4L * F] = Sc[256 + q] - gsign * b2;
+      }
+    } else {
+      if (closer)
+        fp[(long)d * F + f] =
+            fp_close(Sc[q], Sc[64 + q], Sc[128 + q], Sc[192 + q], Sc[256 + q],
+                     gsign, a1, b1, a3, a2, b2);
+    }
   }
 }
 
@@ -1293,6 +1321,63 @@ extern "C" __global__ __launch_bounds__(256) void sigdots_block_kernel(
   }
 }
 
+// Plan and launch the draw-looping solve (mp <= 64) in either mode:
+// PRODS = false stores Fp into out (P,D,F), PRODS = true the five
+// products into out (P,D,5,F).  draws_per_block > 0 forces the slice
+// length (tests); 0 sizes it from the resident workgroup slots
+// (occupancy query x ncu): 64 draws where the launch allows — the
+// one-time RHS load is then under 2% of a slice's traffic — and fewer
+// when that would leave the launch under 8 rounds of resident blocks, so
+// the partial last round stays a small fraction; slices are then evened
+// out over D.
+template <bool PRODS>
+static int launch_draws(const double* L, const double* invd,
+                        const double* RHS, const double* sNs,
+                        const double* sNr, int mp, int F, int D, int P,
+                        double gsign, double* out, int draws_per_block,
+                        int ncu, int lead, hipStream_t stream) {
+  if (lead < 0 || lead > 12 || (lead & 3)) return (int)hipErrorInvalidValue;
+  const int ntile = (F + DL_FREQS - 1) / DL_FREQS;
+  int dpb = draws_per_block, nsl = 0;
+  auto plan = [&](auto kern) -> long {
+    if (dpb <= 0) {
+      int per_cu = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512,
+                                                       0) != hipSuccess ||
+          per_cu < 1)
+        per_cu = 1;
+      const long slots = (long)per_cu * ncu;
+      const long units = (long)P * ntile * D;  // (tile, draw) pairs
+      dpb = (int)std::min<long>(64, std::max<long>(1, units / (8 * slots)));
+      dpb = std::min(dpb, D);
+      const int n = (D + dpb - 1) / dpb;
+      dpb = (D + n - 1) / n;
+    }
+    dpb = std::min(dpb, D);
+    nsl = (D + dpb - 1) / dpb;
+    return ((long)P * nsl + 7) / 8 * 8 * ntile;
+  };
+  if (mp < 16 || mp > 64 || (mp & 15)) return (int)hipErrorInvalidValue;
+  switch ((mp >> 4) * 4 + (lead >> 2)) {
+#define DRAWS_CASE(NBT, SKIP) \
+    case NBT * 4 + SKIP: { \
+      auto kern = trsm_fp_draws_kernel<NBT, SKIP, PRODS>; \
+      const long nblk = plan(kern); \
+      if (nblk >= (1L << 31)) return (int)hipErrorInvalidValue; \
+      hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), 0, stream, \
+                         L, invd, RHS, sNs, sNr, F, D, P, dpb, nsl, gsign, \
+                         out); \
+    } break;
+#define DRAWS_NBT(NBT) \
+    DRAWS_CASE(NBT, 0) DRAWS_CASE(NBT, 1) DRAWS_CASE(NBT, 2) DRAWS_CASE(NBT, 3)
+    DRAWS_NBT(1) DRAWS_NBT(2) DRAWS_NBT(3) DRAWS_NBT(4)
+#undef DRAWS_NBT
+#undef DRAWS_CASE
+    default: return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
+}
+
 // ---------------------------------------------------------------------
 // host-side launchers (called from bindings.cpp).  Each returns the
 // hipError_t of its launch as an int (0 = success); a solve dimension
@@ -1372,58 +1457,26 @@ int launch_trsm_fp(const double* L, const double* invd, const double* RHS,
 // frequencies per workgroup tile of the draw-looping solve
 int trsm_fp_draws_tile_freqs() { return DL_FREQS; }
 
-// Draw-looping solve (mp <= 64), plain stores into fp (P,D,F).
-// draws_per_block > 0 forces the slice length (tests); 0 sizes it from
-// the resident workgroup slots (occupancy query x ncu): 64 draws where
-// the launch allows — the one-time RHS load is then under 2% of a
-// slice's traffic — and fewer when that would leave the launch under 8
-// rounds of resident blocks, so the partial last round stays a small
-// fraction; slices are then evened out over D.
+// Draw-looping solve (mp <= 64), plain stores into fp (P,D,F); the
+// planning is launch_draws'.
 int launch_trsm_fp_draws(const double* L, const double* invd,
                          const double* RHS, const double* sNs,
                          const double* sNr, int mp, int F, int D, int P,
                          double gsign, double* fp, int draws_per_block,
                          int ncu, int lead, hipStream_t stream) {
-  if (lead < 0 || lead > 12 || (lead & 3)) return (int)hipErrorInvalidValue;
-  const int ntile = (F + DL_FREQS - 1) / DL_FREQS;
-  int dpb = draws_per_block, nsl = 0;
-  auto plan = [&](auto kern) -> long {
-    if (dpb <= 0) {
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512,
-                                                       0) != hipSuccess ||
-          per_cu < 1)
-        per_cu = 1;
-      const long slots = (long)per_cu * ncu;
-      const long units = (long)P * ntile * D;  // (tile, draw) pairs
-      dpb = (int)std::min<long>(64, std::max<long>(1, units / (8 * slots)));
-      dpb = std::min(dpb, D);
-      const int n = (D + dpb - 1) / dpb;
-      dpb = (D + n - 1) / n;
-    }
-    dpb = std::min(dpb, D);
-    nsl = (D + dpb - 1) / dpb;
-    return ((long)P * nsl + 7) / 8 * 8 * ntile;
-  };
-  if (mp < 16 || mp > 64 || (mp & 15)) return (int)hipErrorInvalidValue;
-  switch ((mp >> 4) * 4 + (lead >> 2)) {
-#define DRAWS_CASE(NBT, SKIP) \
-    case NBT * 4 + SKIP: { \
-      auto kern = trsm_fp_draws_kernel<NBT, SKIP>; \
-      const long nblk = plan(kern); \
-      if (nblk >= (1L << 31)) return (int)hipErrorInvalidValue; \
-      hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(512), 0, stream, \
-                         L, invd, RHS, sNs, sNr, F, D, P, dpb, nsl, gsign, \
-                         fp); \
-    } break;
-#define DRAWS_NBT(NBT) \
-    DRAWS_CASE(NBT, 0) DRAWS_CASE(NBT, 1) DRAWS_CASE(NBT, 2) DRAWS_CASE(NBT, 3)
-    DRAWS_NBT(1) DRAWS_NBT(2) DRAWS_NBT(3) DRAWS_NBT(4)
-#undef DRAWS_NBT
-#undef DRAWS_CASE
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  return launch_draws<false>(L, invd, RHS, sNs, sNr, mp, F, D, P, gsign, fp,
+                             draws_per_block, ncu, lead, stream);
+}
+
+// Products mode of the draw-looping solve: plain stores into out
+// (P,D,5,F), the layout and the bits of launch_trsm_prods.
+int launch_trsm_prods_draws(const double* L, const double* invd,
+                            const double* RHS, const double* sNs,
+                            const double* sNr, int mp, int F, int D, int P,
+                            double gsign, double* out, int draws_per_block,
+                            int ncu, int lead, hipStream_t stream) {
+  return launch_draws<true>(L, invd, RHS, sNs, sNr, mp, F, D, P, gsign, out,
+                            draws_per_block, ncu, lead, stream);
 }
 
 // Products mode (Fe): one launch over (ftiles, D, P), mp <= 128.

@@ -18,7 +18,10 @@ times the factor kernel alone (chol_batch_into) at the stacked shape;
 defaults P=67, D=1024, m=60 (mp = 64).
 
 times the Fe-on-device kernels (trsm_prods, fe_assemble, fe_skymax);
-defaults P=67, D=256, F=200, nsky=768, m=120.
+defaults P=67, D=256, F=200, nsky=768, m=120.  It also times the
+products solve at the compressed shape (m / 2 variable columns padded in
+front to mp, gsign = -1): trsm_prods and trsm_prods_store on the same
+padded system.
 """
 
 import sys
@@ -219,7 +222,48 @@ def main_fe(P=67, D=256, F=200, nsky=768, m=120):
     flops = P * D * (mp * mp / 2) * (2 * F + 2) * 2
     print(f"trsm_prods  P={P} D={D} F={F} mp={mp}: {t*1e3:9.3f} ms"
           f"  {flops/t/1e12:6.2f} TF/s")
-    del L, invd, out, TNT, phiinv
+    del L, invd
+
+    # the compressed shape: m_v = m / 2 variable columns, padded in
+    # FRONT to mp_v as the engine's compressed stack presents it
+    # (identity block, zero RHS rows on top), gsign = -1.  trsm_prods
+    # and trsm_prods_store on the SAME padded system: the first against
+    # the line above is the dimension change, the second against the
+    # first the draw loop.
+    mv = m // 2
+    mpv = (mv + 15) // 16 * 16
+    lead = mpv - mv
+    skip = lead - lead % 4
+    A = torch.zeros((P, mpv, mpv), dtype=torch.float64, device=DEV)
+    A[:, :lead, :lead] = torch.eye(lead, dtype=torch.float64, device=DEV)
+    A[:, lead:, lead:] = TNT[:, :mv, :mv]
+    pad = torch.nn.functional.pad(phiinv[:, :, :mv], (lead, 0)).contiguous()
+    RHSv = torch.zeros((P, mpv, 2 * F + 1), dtype=torch.float64, device=DEV)
+    RHSv[:, lead:] = torch.as_tensor(
+        rng.normal(size=(P, mv, 2 * F + 1)) * 1e6, device=DEV)
+    L, invd = ext.chol_batch(A, pad, mpv)
+    ref = torch.full_like(out, float("nan"))
+    out.fill_(float("nan"))
+    ext.trsm_prods(L, invd, RHSv, sNs, sNr, ref, -1.0)
+    ext.trsm_prods_store(L, invd, RHSv, sNs, sNr, out, -1.0, lead=skip)
+    assert torch.equal(ref, out), "trsm_prods_store != trsm_prods"
+    flops = P * D * (mpv * mpv / 2) * (2 * F + 2) * 2
+    # alternate the two arms; the spread over rounds is the run-to-run
+    # spread that the comparison has to clear
+    ts = {"trsm_prods": [], "trsm_prods_store": []}
+    for _ in range(5):
+        ts["trsm_prods"].append(timeit(
+            lambda: ext.trsm_prods(L, invd, RHSv, sNs, sNr, ref, -1.0),
+            iters=30, warmup=3))
+        ts["trsm_prods_store"].append(timeit(
+            lambda: ext.trsm_prods_store(L, invd, RHSv, sNs, sNr, out, -1.0,
+                                         lead=skip), iters=30, warmup=3))
+    for name, v in ts.items():
+        t = float(np.median(v))
+        tag = f"{name} P={P} D={D} F={F} mp={mpv} lead={skip}"
+        print(f"{tag}: {t*1e3:9.3f} ms  {flops/t/1e12:6.2f} TF/s"
+              f"  (5 rounds: min {min(v)*1e3:.3f}, max {max(v)*1e3:.3f})")
+    del L, invd, out, ref, TNT, phiinv, A, pad, RHSv
 
     prods = np.empty((P, D, 5, F))
     prods[:, :, 0] = rng.uniform(1.0, 2.0, (P, D, F))
