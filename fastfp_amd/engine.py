@@ -178,6 +178,12 @@ class PulsarBlock:
         self.comp = None  # SolveSystem(G, K, M0, N0, -1, var, delta0)
 
 
+# Smallest compression margin (FpEngine.compression_margin: phiinv_d /
+# delta0) at which a draw still runs the Schur-compressed system; below
+# it callers take the exact direct path.
+COMPRESSION_MARGIN_GUARD = 1.5
+
+
 class FpEngine:
     """Restructured Fp/NM-Fp compute over a list of pulsars.
 
@@ -325,7 +331,7 @@ class FpEngine:
             # spectrum scale (measured: 100x better than the r01
             # 1e-10, which left 6/67 bench pulsars over the probe tol).
             # The margin guard (compression_margin) falls back to the
-            # direct path below margin 1.5.
+            # direct path below COMPRESSION_MARGIN_GUARD.
             # rank-deficient TNT (basis larger than the TOA count)
             # leaves Sigma_0 supported only by the jitter along its
             # null space — keep such pulsars on the exact direct path
@@ -545,15 +551,51 @@ class FpEngine:
 
     def compression_margin(self, phiinvs) -> float:
         """min over pulsars/draws/bins of phiinv_d / delta_0.  The
-        compressed path is numerically safe above ~1.5 (the split is
-        algebraically exact; precision of the Delta = phiinv - delta0
-        subtraction degrades as eps/(1 - 1/margin) and Delta <= 0 is
-        the NaN cliff — measured 2e-10 error at margin 1.7).  Callers
-        fall back to the exact direct path below 1.5.
+        compressed path is numerically safe above
+        ``COMPRESSION_MARGIN_GUARD`` (the split is algebraically exact;
+        precision of the Delta = phiinv - delta0 subtraction degrades
+        as eps/(1 - 1/margin) and Delta <= 0 is the NaN cliff —
+        measured 2e-10 error at margin 1.7).  Callers fall back to the
+        exact direct path below the guard.
 
         One device sync total (a per-pulsar ``float()`` cost 67 syncs
         per draw batch in the CLI hot loop)."""
         return float(self.compression_margin_per_draw(phiinvs).min())
+
+    def margin_split(self, phiinvs, compressed, direct, dim: int = 0):
+        """The per-draw hybrid: ``compressed(rows)`` on the draws whose
+        compression margin reaches ``COMPRESSION_MARGIN_GUARD``,
+        ``direct(rows)`` on the (rare) prior-corner draws below it —
+        ``rows`` being ``phiinvs`` cut to those draws — and the two
+        results scattered back in draw order along ``dim``.  One
+        extreme draw does not take a whole batch off the fast path."""
+        bad = (self.compression_margin_per_draw(phiinvs)
+               < COMPRESSION_MARGIN_GUARD)
+        if not bool(bad.any()):
+            return compressed(phiinvs)
+        out = None
+        for idx, run in ((torch.nonzero(~bad).reshape(-1), compressed),
+                         (torch.nonzero(bad).reshape(-1), direct)):
+            if not len(idx):
+                continue
+            part = run([p[idx.to(p.device)] for p in phiinvs])
+            if out is None:
+                shape = list(part.shape)
+                shape[dim] = bad.shape[0]
+                out = part.new_empty(shape)
+            out.index_copy_(dim, idx.to(out.device), part)
+        return out
+
+    def compress_around_first_draw(self, rn_sigs, samples):
+        """:meth:`enable_draw_compression` for the phi containers
+        ``rn_sigs``, with the fixed phi^-1 taken at the first draw of
+        ``samples`` (any parameter point serves: the variable bins are
+        zeroed inside)."""
+        probe = {k: (v[0] if np.ndim(v) else v) for k, v in samples.items()}
+        return self.enable_draw_compression(
+            [sig.var_slice for sig in rn_sigs],
+            [sig.get_phiinv(probe) for sig in rn_sigs],
+        )
 
     def disable_draw_compression(self):
         for blk in self.blocks:
@@ -571,10 +613,8 @@ class FpEngine:
         ``sigma``: a caller-supplied dense A + diag(d) for the eager
         path (the ``get_mats_fp`` contract)."""
         if self._use_hip and diag.is_cuda:
-            ops.chol_trsm_fp_accum(
-                system.A, diag, system.RHS, system.S, system.R, fp_out,
-                gsign=system.gsign,
-            )
+            L, invd = ops.chol_factor(system.A, diag, ext=self._ext)
+            self._solve(system, L, invd, fp_out, accumulate=True)
             return
         if sigma is None:
             sigma = system.A[None, :, :] + torch.diag_embed(diag)
@@ -622,7 +662,8 @@ class FpEngine:
         ):
             stack = self._direct_stack
         if stack is not None:
-            self._sweep_stacked(stack, rows, fp, draw_chunk)
+            # one chol + one trsm launch per draw chunk across ALL pulsars
+            self._solve_chunks(stack, rows, draw_chunk, fp, pipeline=True)
             return fp[0] if not batched else fp
 
         fp_side = None
@@ -673,23 +714,63 @@ class FpEngine:
 
         return fp[0] if not batched else fp
 
-    def _pipeline_chunks(self, chunks, P, mp, F, fp, fp_pp, factor_into,
-                         solve):
-        """Factor/solve software pipeline over draw chunks with
-        PING-PONG factor buffers and two-way event fencing.
+    # Fewest draws in a chunk for which a sweep solves with the
+    # draw-looping kernel (trsm_fp_store / trsm_prods_store, mp <= 64);
+    # below it the one-draw-per-workgroup kernel runs.
+    # docs/TUNING_NOTES.md has the measurement behind the value.
+    DRAW_LOOP_MIN_DRAWS = 16
+    DRAW_LOOP_MAX_MP = 64
+
+    def _draw_loop_solve(self, sy: SolveSystem, ndraws: int,
+                         prods: bool = False) -> bool:
+        """Whether ``ndraws`` draws of ``sy`` solve with the
+        draw-looping kernel."""
+        # unmeasured: the stacked DIRECT products never take the draw
+        # loop, the per-pulsar direct ones do (docs/ROADMAP.md)
+        if prods and sy.A.dim() == 3 and sy.delta0 is None:
+            return False
+        return (ops.pad16(sy.A.shape[-1]) <= self.DRAW_LOOP_MAX_MP
+                and ndraws >= self.DRAW_LOOP_MIN_DRAWS)
+
+    def _solve(self, sy: SolveSystem, L, invd, out, prods=False,
+               accumulate=False):
+        """Solve ``sy`` on its factor ``L``/``invd`` into the contiguous
+        ``out``: Fp ((P,) D, F), or with ``prods`` the five products
+        ((P,) D, 5, F).  Every entry of ``out`` is overwritten, unless
+        ``accumulate`` asks to add Fp to what ``out`` holds.  The one
+        place that chooses among the four solve kernels."""
+        ext = self._ext
+        args = (L, invd, sy.RHS, sy.S, sy.R, out, sy.gsign)
+        ndraws = out.shape[sy.A.dim() - 2]
+        if not accumulate and self._draw_loop_solve(sy, ndraws, prods):
+            op = ext.trsm_prods_store if prods else ext.trsm_fp_store
+            # the solve skips whole 4-row k-steps of the leading pad
+            op(*args, lead=sy.lead - sy.lead % 4)
+        elif prods:
+            ext.trsm_prods(*args)
+        else:
+            if not accumulate:
+                out.zero_()
+            ext.trsm_fp_accum(*args)
+
+    def _pipeline_chunks(self, sy: SolveSystem, diag, chunks):
+        """``(lo, hi, L, invd)`` per draw chunk of a stacked system
+        within ``MAX_MP_CHOL``, from a factor/solve software pipeline
+        with PING-PONG factor buffers and two-way event fencing.
 
         Chunk k+1's factor (side stream, buffer (k+1)&1) overlaps chunk
-        k's solve (main stream); before overwriting a buffer, the side
-        stream waits on the event recorded after the solve that last
-        read it.  Explicit reusable buffers instead of per-chunk
+        k's solve, which the consumer queues on the main stream before
+        it asks for the next chunk; before overwriting a buffer, the
+        side stream waits on the event recorded after the solve that
+        last read it.  Explicit reusable buffers instead of per-chunk
         allocations + record_stream: the latter defers caching-
         allocator reuse across streams and measured as multi-GB
         allocator churn (2.2 s/step) on the 9.5 GB direct-path chunks.
         The structure is hipGraph-capturable (events + two streams
         forked from the capture stream)."""
         dev = self.device
-        chunk0 = chunks[0][1] - chunks[0][0]
-        nmax = P * chunk0
+        P, mp = sy.A.shape[0], ops.pad16(sy.A.shape[-1])
+        nmax = P * (chunks[0][1] - chunks[0][0])
         key = ("pipebuf", nmax, mp)
         bufs = self._pipe_bufs
         if bufs is None or bufs[0] != key:
@@ -708,11 +789,12 @@ class FpEngine:
         solve_done = [None, None]  # event after the solve reading buf b
 
         def factor(i, lo, hi):
-            b = i & 1
+            b, n = i & 1, P * (hi - lo)
             with torch.cuda.stream(side):
                 if solve_done[b] is not None:
                     side.wait_event(solve_done[b])
-                factor_into(Lb[b], Ib[b], lo, hi)
+                self._ext.chol_batch_into(sy.A, diag(lo, hi), mp,
+                                          Lb[b][:n], Ib[b][:n])
                 ev = torch.cuda.Event()
                 ev.record(side)
             return ev
@@ -723,95 +805,72 @@ class FpEngine:
             if i + 1 < len(chunks):
                 pending = factor(i + 1, *chunks[i + 1])
             main.wait_event(ev)
-            b = i & 1
-            if hi - lo == fp_pp.shape[1]:
-                pp = fp_pp
-            else:
-                pp = torch.empty((P, hi - lo, F), dtype=torch.float64,
-                                 device=dev)
-            solve(Lb[b], Ib[b], lo, hi, pp)  # writes every entry of pp
-            fp[lo:hi] += pp.sum(dim=0)
+            b, n = i & 1, P * (hi - lo)
+            yield lo, hi, Lb[b][:n], Ib[b][:n]
+            # resumed once the consumer has queued its solve of buffer b
             ev2 = torch.cuda.Event()
             ev2.record(main)
             solve_done[b] = ev2
 
-    # Fewest draws in a chunk for which the stacked sweep solves with
-    # the draw-looping kernel (trsm_fp_store, mp <= 64); below it the
-    # one-draw-per-workgroup kernel runs.  docs/TUNING_NOTES.md has the
-    # measurement behind the value.
-    DRAW_LOOP_MIN_DRAWS = 16
-    DRAW_LOOP_MAX_MP = 64
-
-    def _draw_loop_solve(self, mp: int, ndraws: int) -> bool:
-        return (mp <= self.DRAW_LOOP_MAX_MP
-                and ndraws >= self.DRAW_LOOP_MIN_DRAWS)
-
-    def _stacked_chunks(self, st: SolveSystem, rows, draw_chunk):
-        """Draw chunks of a stacked sweep: the ``(lo, hi)`` list and a
-        function giving a chunk's contiguous (P, hi-lo, m) diagonal.
-        The per-pulsar rows are gathered and stacked once."""
-        pinv = torch.stack([p[:, v] for p, v in zip(rows, st.var)])  # (P, D, m)
-        D = pinv.shape[1]
+    def _solve_chunks(self, sy: SolveSystem, rows, draw_chunk, out,
+                      prods=False, pipeline=False):
+        """The one driver of the HIP sweeps: walk the draws of ``rows``
+        (the (D, m) phiinv rows of one pulsar, or the list of them for a
+        stack) in chunks — diagonal, factor, solve into a contiguous
+        per-chunk buffer.  With ``prods`` the products land in ``out``
+        ((P,) D, 5, F); otherwise (stacked only) the chunk's per-pulsar
+        Fp planes are summed, deterministically by torch, into ``out``
+        (D, F)."""
+        if sy.A.dim() == 3:  # gathered and stacked once: (P, D, m_var)
+            pinv = torch.stack([p[:, v] for p, v in zip(rows, sy.var)])
+        else:
+            pinv = rows[:, sy.var]
+        D = pinv.shape[-2]
         chunks = [(lo, min(lo + draw_chunk, D))
                   for lo in range(0, D, draw_chunk)]
-        return chunks, lambda lo, hi: st.diag(pinv[:, lo:hi, :]).contiguous()
-
-    def _sweep_stacked(self, st: SolveSystem, rows, fp, draw_chunk):
-        """Pulsar-batched sweep of a stacked system: one chol + one
-        trsm launch per draw chunk across ALL pulsars, accumulated into
-        ``fp`` (D, F)."""
-        ext = self._ext
-        P, F = len(rows), fp.shape[1]
-        chunks, diag = self._stacked_chunks(st, rows, draw_chunk)
-        fp_pp = torch.empty((P, chunks[0][1], F), dtype=torch.float64,
-                            device=self.device)
-        mp = ops.pad16(st.A.shape[-1])
-        # the solve skips whole 4-row k-steps of the leading pad
-        skip = st.lead - st.lead % 4
-        if len(chunks) > 1 and mp <= ops.MAX_MP_CHOL:
-            # SOFTWARE PIPELINE across draw chunks: chunk k+1's factor
-            # runs on a side stream beside chunk k's solve.  The solve
-            # kernels fill the register file (4 waves/SIMD at 128
-            # VGPR), so a CU that takes factor workgroups gives up
-            # solve workgroups for as long as they live: measured, the
-            # step pays about 0.8 of the factor's stand-alone time per
-            # chunk, and the pipeline hides the other fifth
-            # (docs/TUNING_NOTES.md).  Above MAX_MP_CHOL the factor is
-            # rocSOLVER's, which does not write into caller buffers.
-            def factor_into(L, invd, lo, hi):
-                n = P * (hi - lo)
-                ext.chol_batch_into(st.A, diag(lo, hi), mp, L[:n], invd[:n])
-
-            def solve(L, invd, lo, hi, pp):
-                n = P * (hi - lo)
-                if self._draw_loop_solve(mp, hi - lo):
-                    ext.trsm_fp_store(L[:n], invd[:n], st.RHS, st.S, st.R,
-                                      pp, st.gsign, lead=skip)
-                else:
-                    pp.zero_()
-                    ext.trsm_fp_accum(L[:n], invd[:n], st.RHS, st.S, st.R,
-                                      pp, st.gsign)
-
-            self._pipeline_chunks(chunks, P, mp, F, fp, fp_pp,
-                                  factor_into, solve)
+        if not chunks:
             return
 
-        for lo, hi in chunks:
-            d = diag(lo, hi)
-            if hi - lo == fp_pp.shape[1]:
-                pp = fp_pp
-            else:  # tail chunk: a dim-1 slice would be non-contiguous
-                pp = torch.empty((P, hi - lo, F), dtype=torch.float64,
-                                 device=self.device)
-            if self._draw_loop_solve(mp, hi - lo):
-                L, invd = ext.chol_batch(st.A, d, mp)
-                ext.trsm_fp_store(L, invd, st.RHS, st.S, st.R, pp, st.gsign,
-                                  lead=skip)
+        def diag(lo, hi):
+            return sy.diag(pinv[..., lo:hi, :]).contiguous()
+
+        def empty(n):  # what the solve writes for n draws
+            return torch.empty(
+                pinv.shape[:-2] + (n,) + out.shape[-2 if prods else -1:],
+                dtype=torch.float64, device=self.device)
+
+        # SOFTWARE PIPELINE across the chunks of a stacked Fp sweep:
+        # chunk k+1's factor runs on a side stream beside chunk k's
+        # solve.  The solve kernels fill the register file (4 waves/SIMD
+        # at 128 VGPR), so a CU that takes factor workgroups gives up
+        # solve workgroups for as long as they live: measured, the step
+        # pays about 0.8 of the factor's stand-alone time per chunk, and
+        # the pipeline hides the other fifth (docs/TUNING_NOTES.md).
+        # Above MAX_MP_CHOL the factor is rocSOLVER's, which does not
+        # write into caller buffers.
+        if (pipeline and len(chunks) > 1
+                and ops.pad16(sy.A.shape[-1]) <= ops.MAX_MP_CHOL):
+            factors = self._pipeline_chunks(sy, diag, chunks)
+        else:
+            factors = ((lo, hi, *ops.chol_factor(sy.A, diag(lo, hi),
+                                                 ext=self._ext))
+                       for lo, hi in chunks)
+        n0 = chunks[0][1]
+        # products go straight into `out` where its draw slices are
+        # contiguous (one pulsar, or a single chunk); otherwise through
+        # one full-size buffer, and a tail chunk through its own
+        inplace = prods and out[..., :n0, :, :].is_contiguous()
+        full = None if inplace else empty(n0)
+        for lo, hi, L, invd in factors:
+            if inplace:
+                buf = out[..., lo:hi, :, :]
             else:
-                pp.zero_()
-                ops.chol_trsm_fp_accum(st.A, d, st.RHS, st.S, st.R, pp,
-                                       gsign=st.gsign)
-            fp[lo:hi] += pp.sum(dim=0)
+                buf = full if hi - lo == n0 else empty(hi - lo)
+            self._solve(sy, L, invd, buf, prods)
+            if not prods:
+                out[lo:hi] += buf.sum(dim=0)
+            elif not inplace:
+                out[..., lo:hi, :, :] = buf
 
     def sweep_products(self, sigmas=None, phiinvs=None,
                        compressed: bool = False) -> torch.Tensor:
@@ -896,73 +955,31 @@ class FpEngine:
         No limit on ``m`` and no common basis size is needed.  The
         per-draw margin is the caller's business, as in :meth:`sweep`."""
         assert self.freqs is not None, "call precompute(freqs) first"
-        if compressed:
-            if not self._use_hip:
-                return self.sweep_products(phiinvs=phiinvs, compressed=True)
-            if any(blk.comp is not None for blk in self.blocks):
-                return self._products_compressed_hip(phiinvs, draw_chunk)
-        st = self._direct_stack
-        if st is None or ops.pad16(st.A.shape[-1]) > ops.MAX_MP_CHOL:
-            return self.sweep_products(phiinvs=phiinvs)
+        if compressed and not self._use_hip:
+            return self.sweep_products(phiinvs=phiinvs, compressed=True)
+        compressed = compressed and any(
+            blk.comp is not None for blk in self.blocks)
+        st = self._comp_stack if compressed else self._direct_stack
+        if st is None:  # the compressed systems also solve one by one
+            eager = not compressed
+        else:
+            eager = ops.pad16(st.A.shape[-1]) > ops.MAX_MP_CHOL
+        if eager:
+            return self.sweep_products(phiinvs=phiinvs, compressed=compressed)
         rows, batched = self._rows(phiinvs)
-        out = self._products_stacked(st, rows, draw_chunk)
-        return out if batched else out[:, 0]
-
-    def _products_stacked(self, st: SolveSystem, rows, draw_chunk):
-        """(P, D, 5, F) products of a stacked system within
-        ``MAX_MP_CHOL``: one factor and one solve launch per draw
-        chunk."""
-        ext = self._ext
-        mp = ops.pad16(st.A.shape[-1])
-        skip = st.lead - st.lead % 4
-        P, D, F = len(rows), rows[0].shape[0], self.freqs.shape[0]
-        chunks, diag = self._stacked_chunks(st, rows, draw_chunk)
-        out = torch.empty((P, D, 5, F), dtype=torch.float64,
-                          device=self.device)
-        for lo, hi in chunks:
-            L, invd = ext.chol_batch(st.A, diag(lo, hi), mp)
-            # a draw slice of `out` is not contiguous
-            part = out if (lo, hi) == (0, D) else torch.empty(
-                (P, hi - lo, 5, F), dtype=torch.float64, device=self.device)
-            if st.delta0 is not None and self._draw_loop_solve(mp, hi - lo):
-                ext.trsm_prods_store(L, invd, st.RHS, st.S, st.R, part,
-                                     st.gsign, lead=skip)
-            else:
-                ext.trsm_prods(L, invd, st.RHS, st.S, st.R, part, st.gsign)
-            if part is not out:
-                out[:, lo:hi] = part
-        return out
-
-    def _products_compressed_hip(self, phiinvs, draw_chunk):
-        """``sweep_products_hip(compressed=True)`` on a HIP engine with
-        at least one compressed pulsar."""
-        rows, batched = self._rows(phiinvs)
-        st = self._comp_stack
+        out = torch.empty(
+            (len(rows), rows[0].shape[0], 5, self.freqs.shape[0]),
+            dtype=torch.float64, device=self.device)
         if st is not None:
-            if ops.pad16(st.A.shape[-1]) > ops.MAX_MP_CHOL:
-                return self.sweep_products(phiinvs=phiinvs, compressed=True)
-            out = self._products_stacked(st, rows, draw_chunk)
+            # one factor and one solve launch per draw chunk
+            self._solve_chunks(st, rows, draw_chunk, out, prods=True)
             return out if batched else out[:, 0]
-        ext = self._ext
-        D, F = rows[0].shape[0], self.freqs.shape[0]
-        out = torch.empty((len(rows), D, 5, F), dtype=torch.float64,
-                          device=self.device)
+        # compressed without a stack: per pulsar, each on its own system
         for i, (blk, p) in enumerate(zip(self.blocks, rows)):
             sy = blk.comp if blk.comp is not None else blk.direct
-            mp = ops.pad16(sy.A.shape[-1])
-            if mp > ops.MAX_MP_CHOL:
+            if ops.pad16(sy.A.shape[-1]) > ops.MAX_MP_CHOL:
                 out[i] = torch.stack(
                     _eager_products(sy, self._dense(sy, p)), dim=1)
-                continue
-            for lo in range(0, D, draw_chunk):
-                hi = min(lo + draw_chunk, D)
-                d = sy.diag(p[lo:hi, sy.var]).contiguous()
-                L, invd = ext.chol_batch(sy.A, d, mp)
-                part = out[i, lo:hi]  # (Dc, 5, F), contiguous
-                if self._draw_loop_solve(mp, hi - lo):
-                    ext.trsm_prods_store(L, invd, sy.RHS, sy.S, sy.R, part,
-                                         sy.gsign)
-                else:
-                    ext.trsm_prods(L, invd, sy.RHS, sy.S, sy.R, part,
-                                   sy.gsign)
+            else:
+                self._solve_chunks(sy, p, draw_chunk, out[i], prods=True)
         return out if batched else out[:, 0]

@@ -362,24 +362,17 @@ class NMFe:
         engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
         engine.precompute(freqs, freq_chunk=freq_chunk)
         if compress:
-            # fixed phi^-1 from any parameter point; variable bins are
-            # zeroed inside enable_draw_compression
-            probe = {k: (v[0] if np.ndim(v) else v)
-                     for k, v in samples.items()}
-            engine.enable_draw_compression(
-                [sig.var_slice for sig in self.rn_sigs],
-                [sig.get_phiinv(probe) for sig in self.rn_sigs],
-            )
+            engine.compress_around_first_draw(self.rn_sigs, samples)
         return engine
 
     @staticmethod
     def _products(engine, chunk, compress: bool, hip: bool):
         """(P, Dc, 5, F) products of one draw chunk, on the HIP solve
         (``hip``) or the eager one.  With ``compress``, the per-draw
-        guard of ``NMFp.sweep``: draws whose compression margin is at
-        least 1.5 go through the compressed systems, the (rare)
-        prior-corner draws through the exact direct ones, and the rows
-        are scattered back in order."""
+        guard of ``NMFp.sweep`` (``FpEngine.margin_split``): draws whose
+        compression margin reaches the guard go through the compressed
+        systems, the (rare) prior-corner draws through the exact direct
+        ones, and the rows are scattered back in order."""
         if hip:
             run = engine.sweep_products_hip
         else:
@@ -389,20 +382,8 @@ class NMFe:
             return run(chunk)
         # one copy to the engine's device serves the margin and the solve
         chunk = [p.to(engine.device) for p in chunk]
-        bad = engine.compression_margin_per_draw(chunk) < 1.5
-        if not bool(bad.any()):
-            return run(chunk, compressed=True)
-        out = None
-        for idx, comp in ((torch.nonzero(~bad).reshape(-1), True),
-                          (torch.nonzero(bad).reshape(-1), False)):
-            if not len(idx):
-                continue
-            part = run([p[idx.to(p.device)] for p in chunk], compressed=comp)
-            if out is None:
-                out = part.new_empty((part.shape[0], bad.shape[0])
-                                     + tuple(part.shape[2:]))
-            out[:, idx.to(out.device)] = part
-        return out
+        return engine.margin_split(
+            chunk, lambda rows: run(rows, compressed=True), run, dim=1)
 
     def sweep(
         self,

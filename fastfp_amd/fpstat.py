@@ -16,7 +16,7 @@ import math
 import numpy as np
 import torch
 
-from fastfp_amd.engine import FpEngine
+from fastfp_amd.engine import COMPRESSION_MARGIN_GUARD, FpEngine
 from fastfp_amd.xcy import get_xCy
 
 
@@ -103,9 +103,10 @@ class FastFp:
             # phi/jitter margin the Woodbury correction relies on.  In
             # either case fall back to the CPU LAPACK engine — slower
             # but always exact.
-            # threshold 1.5: see the margin-guard note in nmfp.sweep
+            # the threshold: see the margin-guard note in nmfp.sweep
             margin = eng.compression_margin(phiinvs)
-            if any(blk.comp is None for blk in eng.blocks) or margin < 1.5:
+            if (any(blk.comp is None for blk in eng.blocks)
+                    or margin < COMPRESSION_MARGIN_GUARD):
                 import warnings
 
                 warnings.warn(

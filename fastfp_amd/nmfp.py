@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from fastfp_amd.engine import FpEngine
+from fastfp_amd.engine import COMPRESSION_MARGIN_GUARD, FpEngine
 from fastfp_amd.xcy import get_xCy
 
 
@@ -122,14 +122,14 @@ class NMFp:
         return fstat
 
     # ------------------------------------------------------------------
-    def _direct_rows(self, engine, phiinvs, bad_idx, draw_chunk, Nvecs, Ts):
-        """Exact direct-path evaluation of the draws at ``bad_idx``.
+    def _direct_rows(self, engine, sub, draw_chunk, Nvecs, Ts):
+        """Exact direct-path evaluation of the (prior-corner) draws
+        ``sub``, per-pulsar (Db, m) phiinv rows.
 
         On GPU with basis size m <= 256 this is the direct HIP solve;
         above 256 (no GPU kernel) the rows run through a cached CPU
         LAPACK eager engine — slow but exact, and only the rare
         prior-corner draws pay it."""
-        sub = [p[bad_idx.to(p.device)] for p in phiinvs]
         if engine._use_hip and any(b.m > 256 for b in engine.blocks):
             fr = engine.freqs.cpu().numpy()
             ce = getattr(self, "_cpu_eng", None)
@@ -204,12 +204,13 @@ class NMFp:
             return None
         fp, phiinvs = g(samples)
         margins = engine.compression_margin_per_draw(phiinvs)
-        bad = margins < 1.5
+        bad = margins < COMPRESSION_MARGIN_GUARD
         if bool(bad.any()):
             bad_idx = torch.nonzero(bad).reshape(-1)
             fp = fp.clone()
-            fp[bad_idx] = self._direct_rows(engine, phiinvs, bad_idx,
-                                            draw_chunk, Nvecs, Ts)
+            fp[bad_idx] = self._direct_rows(
+                engine, [p[bad_idx.to(p.device)] for p in phiinvs],
+                draw_chunk, Nvecs, Ts)
         return fp.cpu().numpy()
 
     # ------------------------------------------------------------------
@@ -239,13 +240,7 @@ class NMFp:
             engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
             engine.precompute(freqs, freq_chunk=freq_chunk)
             if compress:
-                # fixed phi^-1 from any parameter point; variable bins
-                # are zeroed inside enable_draw_compression
-                probe = {k: (v[0] if np.ndim(v) else v) for k, v in samples.items()}
-                engine.enable_draw_compression(
-                    [sig.var_slice for sig in self.rn_sigs],
-                    [sig.get_phiinv(probe) for sig in self.rn_sigs],
-                )
+                engine.compress_around_first_draw(self.rn_sigs, samples)
         from fastfp_amd.noise import batch_phiinv, check_batch_homogeneous
 
         # the homogeneity check device-syncs; cache it across the
@@ -276,27 +271,19 @@ class NMFp:
         # round-1 threshold of 1e3 was ~3 orders too conservative and
         # silently pushed whole uniform-prior sweeps onto the 4x-slower
         # direct path.  The guard is PER DRAW: prior-corner draws
-        # (margin < 1.5) run the exact direct path, the rest stay
-        # compressed — one extreme draw no longer slows a whole batch.
+        # (margin < COMPRESSION_MARGIN_GUARD) run the exact direct path,
+        # the rest stay compressed — one extreme draw no longer slows a
+        # whole batch.
+        def run(rows):
+            return engine.sweep(phiinvs=rows, draw_chunk=draw_chunk)
+
         if compress and any(b.comp is not None for b in engine.blocks):
-            margins = engine.compression_margin_per_draw(phiinvs)
-            bad = margins < 1.5
-            nbad = int(bad.sum())
-            if nbad:
-                good_idx = torch.nonzero(~bad).reshape(-1)
-                bad_idx = torch.nonzero(bad).reshape(-1)
-                D = margins.shape[0]
-                F = engine.freqs.shape[0]
-                fp = torch.zeros((D, F), dtype=torch.float64,
-                                 device=engine.device)
-                if len(good_idx):
-                    sub = [p[good_idx.to(p.device)] for p in phiinvs]
-                    fp[good_idx] = engine.sweep(phiinvs=sub,
-                                                draw_chunk=draw_chunk)
-                fp[bad_idx] = self._direct_rows(engine, phiinvs, bad_idx,
-                                                draw_chunk, Nvecs, Ts)
-                return fp.cpu().numpy()
-        fp = engine.sweep(phiinvs=phiinvs, draw_chunk=draw_chunk)
+            fp = engine.margin_split(
+                phiinvs, run,
+                lambda rows: self._direct_rows(engine, rows, draw_chunk,
+                                               Nvecs, Ts))
+        else:
+            fp = run(phiinvs)
         return fp.cpu().numpy()
 
 

@@ -143,21 +143,21 @@ def freq_precompute_block(toas, block_noise, Nr, V, TNr, freqs):
     return _basis_rhs(V, ones, toas, TNr, freqs), sNs, sNr
 
 
-def chol_trsm_fp_accum(TNT, phiinv, RHS, sNs, sNr, fp_out, gsign=1.0):
-    """Batched Cholesky of Sigma = TNT + diag(phiinv), then the fused
-    triangular solve of RHS (mp, 2F+1) + 2x2 Fp reduction, accumulating
-    into fp_out (D, F).
+def chol_factor(TNT, phiinv, ext=None):
+    """Batched Cholesky of Sigma = TNT + diag(phiinv) as the solve
+    kernels take it: ``(L (P*D, mp, mp), invd (P*D, mp/16, 16, 16))``
+    for TNT (m, m) / (P, m, m) and phiinv (D, m) / (P, D, m).
 
     mp <= 128: LDS-resident chol_batch kernel.  128 < mp <= 256
     (GP-ECORR direct path): Sigma no longer fits LDS — factor through
     batched rocSOLVER Cholesky (substitution-based, accurate; the
     rocBLAS accuracy caveat of docs/TUNING_NOTES.md concerns its
-    inversion-based trsm, not potrf) + the diag_inv kernel, then the
-    same register-resident trsm.
+    inversion-based trsm, not potrf) + the diag_inv kernel.
 
-    ``gsign``: +1 direct path (M = sNs - W.W); -1 Schur-compressed draw
-    path (M = M0 + W.W) — docs/DESIGN.md §draw compression."""
-    ext = _try_load()
+    ``ext``: the extension to launch through (the engine passes its
+    own); the loaded one by default."""
+    if ext is None:
+        ext = _try_load()
     m = TNT.shape[-1]
     mp = check_m(m)
     if mp <= MAX_MP_CHOL:
@@ -176,7 +176,17 @@ def chol_trsm_fp_accum(TNT, phiinv, RHS, sNs, sNr, fp_out, gsign=1.0):
         idx = torch.arange(m, mp, device=TNT.device)
         L[:, idx, idx] = 1.0
         invd = ext.diag_inv(L.contiguous())
-    ext.trsm_fp_accum(L, invd, RHS, sNs, sNr, fp_out, gsign)
+    return L, invd
+
+
+def chol_trsm_fp_accum(TNT, phiinv, RHS, sNs, sNr, fp_out, gsign=1.0):
+    """:func:`chol_factor`, then the fused triangular solve of RHS
+    (mp, 2F+1) + 2x2 Fp reduction, accumulating into fp_out (D, F).
+
+    ``gsign``: +1 direct path (M = sNs - W.W); -1 Schur-compressed draw
+    path (M = M0 + W.W) — docs/DESIGN.md §draw compression."""
+    L, invd = chol_factor(TNT, phiinv)
+    _try_load().trsm_fp_accum(L, invd, RHS, sNs, sNr, fp_out, gsign)
 
 
 # ----------------------------------------------------------------------

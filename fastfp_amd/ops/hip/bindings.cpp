@@ -7,38 +7,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
-extern "C" {
-int launch_sigdots(const double*, const double*, const double*,
-                   const double*, int, int, double*, double*, hipStream_t);
-int launch_sbgemm(const double*, const double*, const double*,
-                  const double*, int, int, int, int, double*, long, long,
-                  int, hipStream_t);
-int launch_chol_batch(const double*, const double*, int, int, int, int,
-                      double*, double*, hipStream_t);
-int launch_trsm_fp(const double*, const double*, const double*,
-                   const double*, const double*, int, int, int, int,
-                   double, double*, hipStream_t);
-int launch_trsm_fp_draws(const double*, const double*, const double*,
-                         const double*, const double*, int, int, int, int,
-                         double, double*, int, int, int, hipStream_t);
-int launch_trsm_prods_draws(const double*, const double*, const double*,
-                            const double*, const double*, int, int, int, int,
-                            double, double*, int, int, int, hipStream_t);
-int trsm_fp_draws_tile_freqs();
-int launch_sigdots_block(const double*, const double*, const double*,
-                         const double*, const double*, const long*,
-                         const long*, int, int, int, double*, double*,
-                         hipStream_t);
-int launch_diag_inv(const double*, int, long, double*, hipStream_t);
-int launch_trsm_prods(const double*, const double*, const double*,
-                      const double*, const double*, int, int, int, int,
-                      double, double*, hipStream_t);
-int fe_max_pulsars();
-int launch_fe_assemble(const double*, const double*, int, int, int, int,
-                       double*, hipStream_t);
-int launch_fe_skymax(const double*, const double*, int, int, int, int,
-                     double*, int*, int*, hipStream_t);
-}
+#include "launchers.h"
 
 namespace {
 
@@ -201,6 +170,57 @@ SolveDims check_solve(const torch::Tensor& L, const torch::Tensor& invd,
   return d;
 }
 
+// What tells the four solve ops apart.
+struct SolveOp {
+  const char* name;     // the Python-visible op
+  bool prods;           // five products (out has a K = 5 dimension), not Fp
+  bool draws;           // the draw-looping kernel
+  int max_mp;           // cap on the padded solve dimension
+  const char* instead;  // where the error sends a caller above the cap
+};
+
+// The one body of the four solve ops: shapes, the op's mp cap, the
+// draw-loop arguments, nothing to do on empty shapes, launch.
+void solve(const SolveOp& op, const torch::Tensor& L,
+           const torch::Tensor& invd, const torch::Tensor& RHS,
+           const torch::Tensor& sNs, const torch::Tensor& sNr,
+           const torch::Tensor& out, const char* oname, double gsign,
+           int64_t draws_per_block = 0, int64_t lead = 0) {
+  const SolveDims d =
+      check_solve(L, invd, RHS, sNs, sNr, out, oname, op.prods ? 5 : 0);
+  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= op.max_mp, op.name,
+              " supports a padded solve dimension mp <= ", op.max_mp,
+              " (multiple of 16); got mp=", d.mp, " — use ", op.instead);
+  if (op.draws) {
+    TORCH_CHECK(draws_per_block >= 0 && draws_per_block < (1L << 31),
+                "draws_per_block must be >= 0");
+    TORCH_CHECK(lead >= 0 && lead <= 12 && lead % 4 == 0,
+                "lead must be 0, 4, 8 or 12; got ", lead);
+  }
+  if (d.D == 0 || d.F == 0 || d.P == 0) return;
+  if (!op.draws) {
+    check_launch(
+        launch_trsm(op.prods, L.data_ptr<double>(), invd.data_ptr<double>(),
+                    RHS.data_ptr<double>(), sNs.data_ptr<double>(),
+                    sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
+                    out.data_ptr<double>(), stream()),
+        op.name);
+    return;
+  }
+  // the factor is fetched with 16-byte loads
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(L.data_ptr<double>()) |
+               reinterpret_cast<uintptr_t>(invd.data_ptr<double>())) % 16 == 0,
+              "L and invd must be 16-byte aligned");
+  const int ncu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  check_launch(
+      launch_trsm_draws(op.prods, L.data_ptr<double>(),
+                        invd.data_ptr<double>(), RHS.data_ptr<double>(),
+                        sNs.data_ptr<double>(), sNr.data_ptr<double>(), d.mp,
+                        d.F, d.D, d.P, gsign, out.data_ptr<double>(),
+                        (int)draws_per_block, ncu, (int)lead, stream()),
+      op.name);
+}
+
 }  // namespace
 
 // trsm_fp_accum: solve + fused 2x2 reduction, accumulating in place
@@ -208,16 +228,9 @@ SolveDims check_solve(const torch::Tensor& L, const torch::Tensor& invd,
 void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                    torch::Tensor sNs, torch::Tensor sNr, torch::Tensor fp,
                    double gsign) {
-  const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, fp, "fp", 0);
-  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 256,
-              "mp must be 16..256, multiple of 16");
-  if (d.D == 0 || d.F == 0 || d.P == 0) return;
-  check_launch(
-      launch_trsm_fp(L.data_ptr<double>(), invd.data_ptr<double>(),
-                     RHS.data_ptr<double>(), sNs.data_ptr<double>(),
-                     sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
-                     fp.data_ptr<double>(), stream()),
-      "trsm_fp_accum");
+  solve({"trsm_fp_accum", false, false, 256,
+         "the Schur-compressed system or the CPU engine"},
+        L, invd, RHS, sNs, sNr, fp, "fp", gsign);
 }
 
 // trsm_fp_store: the same solve and reduction as trsm_fp_accum for
@@ -233,27 +246,8 @@ void trsm_fp_accum(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
 void trsm_fp_store(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                    torch::Tensor sNs, torch::Tensor sNr, torch::Tensor out,
                    double gsign, int64_t draws_per_block, int64_t lead) {
-  const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, out, "out", 0);
-  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 64,
-              "trsm_fp_store supports a padded solve dimension mp <= 64 "
-              "(multiple of 16); got mp=", d.mp, " — use trsm_fp_accum");
-  TORCH_CHECK(draws_per_block >= 0 && draws_per_block < (1L << 31),
-              "draws_per_block must be >= 0");
-  TORCH_CHECK(lead >= 0 && lead <= 12 && lead % 4 == 0,
-              "lead must be 0, 4, 8 or 12; got ", lead);
-  if (d.D == 0 || d.F == 0 || d.P == 0) return;
-  // the factor is fetched with 16-byte loads
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(L.data_ptr<double>()) |
-               reinterpret_cast<uintptr_t>(invd.data_ptr<double>())) % 16 == 0,
-              "L and invd must be 16-byte aligned");
-  const int ncu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-  check_launch(
-      launch_trsm_fp_draws(L.data_ptr<double>(), invd.data_ptr<double>(),
-                           RHS.data_ptr<double>(), sNs.data_ptr<double>(),
-                           sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
-                           out.data_ptr<double>(), (int)draws_per_block, ncu,
-                           (int)lead, stream()),
-      "trsm_fp_store");
+  solve({"trsm_fp_store", false, true, 64, "trsm_fp_accum"}, L, invd, RHS,
+        sNs, sNr, out, "out", gsign, draws_per_block, lead);
 }
 
 // trsm_prods: the same solve as trsm_fp_accum, but the five corrected
@@ -263,18 +257,9 @@ void trsm_fp_store(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
 void trsm_prods(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                 torch::Tensor sNs, torch::Tensor sNr, torch::Tensor out,
                 double gsign) {
-  const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, out, "out", 5);
-  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 128,
-              "trsm_prods supports a padded solve dimension mp <= 128 "
-              "(multiple of 16); got mp=", d.mp,
-              " — use FpEngine.sweep_products for larger bases");
-  if (d.D == 0 || d.F == 0 || d.P == 0) return;
-  check_launch(
-      launch_trsm_prods(L.data_ptr<double>(), invd.data_ptr<double>(),
-                        RHS.data_ptr<double>(), sNs.data_ptr<double>(),
-                        sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P, gsign,
-                        out.data_ptr<double>(), stream()),
-      "trsm_prods");
+  solve({"trsm_prods", true, false, 128,
+         "FpEngine.sweep_products for larger bases"},
+        L, invd, RHS, sNs, sNr, out, "out", gsign);
 }
 
 // trsm_prods_store: the five products of trsm_prods for mp <= 64, by the
@@ -285,27 +270,8 @@ void trsm_prods(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
 void trsm_prods_store(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
                       torch::Tensor sNs, torch::Tensor sNr, torch::Tensor out,
                       double gsign, int64_t draws_per_block, int64_t lead) {
-  const SolveDims d = check_solve(L, invd, RHS, sNs, sNr, out, "out", 5);
-  TORCH_CHECK(d.mp % 16 == 0 && d.mp >= 16 && d.mp <= 64,
-              "trsm_prods_store supports a padded solve dimension mp <= 64 "
-              "(multiple of 16); got mp=", d.mp, " — use trsm_prods");
-  TORCH_CHECK(draws_per_block >= 0 && draws_per_block < (1L << 31),
-              "draws_per_block must be >= 0");
-  TORCH_CHECK(lead >= 0 && lead <= 12 && lead % 4 == 0,
-              "lead must be 0, 4, 8 or 12; got ", lead);
-  if (d.D == 0 || d.F == 0 || d.P == 0) return;
-  // the factor is fetched with 16-byte loads
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(L.data_ptr<double>()) |
-               reinterpret_cast<uintptr_t>(invd.data_ptr<double>())) % 16 == 0,
-              "L and invd must be 16-byte aligned");
-  const int ncu = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
-  check_launch(
-      launch_trsm_prods_draws(L.data_ptr<double>(), invd.data_ptr<double>(),
-                              RHS.data_ptr<double>(), sNs.data_ptr<double>(),
-                              sNr.data_ptr<double>(), d.mp, d.F, d.D, d.P,
-                              gsign, out.data_ptr<double>(),
-                              (int)draws_per_block, ncu, (int)lead, stream()),
-      "trsm_prods_store");
+  solve({"trsm_prods_store", true, true, 64, "trsm_prods"}, L, invd, RHS, sNs,
+        sNr, out, "out", gsign, draws_per_block, lead);
 }
 
 namespace {
@@ -337,11 +303,10 @@ torch::Tensor fe_assemble(torch::Tensor prods, torch::Tensor ant) {
   const int P = prods.size(0), D = prods.size(1), F = prods.size(3);
   const int nsky = ant.size(0);
   auto fe = torch::empty({D, nsky, F}, prods.options());
-  const int err = launch_fe_assemble(prods.data_ptr<double>(),
-                                     ant.data_ptr<double>(), P, D, F, nsky,
-                                     fe.data_ptr<double>(), stream());
-  TORCH_CHECK(err == 0, "fe_assemble launch failed: ",
-              hipGetErrorString((hipError_t)err));
+  check_launch(
+      launch_fe_assemble(prods.data_ptr<double>(), ant.data_ptr<double>(), P,
+                         D, F, nsky, fe.data_ptr<double>(), stream()),
+      "fe_assemble");
   return fe;
 }
 
@@ -356,12 +321,12 @@ std::vector<torch::Tensor> fe_skymax(torch::Tensor prods, torch::Tensor ant) {
   auto femax = torch::full({D, F}, -INFINITY, prods.options());
   auto argmax = torch::full({D, F}, -1, iopts);
   auto nskip = torch::zeros({D, F}, iopts);
-  const int err = launch_fe_skymax(
-      prods.data_ptr<double>(), ant.data_ptr<double>(), P, D, F, nsky,
-      femax.data_ptr<double>(), argmax.data_ptr<int>(),
-      nskip.data_ptr<int>(), stream());
-  TORCH_CHECK(err == 0, "fe_skymax launch failed: ",
-              hipGetErrorString((hipError_t)err));
+  check_launch(
+      launch_fe_skymax(prods.data_ptr<double>(), ant.data_ptr<double>(), P, D,
+                       F, nsky, femax.data_ptr<double>(),
+                       argmax.data_ptr<int>(), nskip.data_ptr<int>(),
+                       stream()),
+      "fe_skymax");
   return {femax, argmax, nskip};
 }
 

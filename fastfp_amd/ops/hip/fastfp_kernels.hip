@@ -39,6 +39,12 @@
 //                        factor (the mp > 128 direct path)
 //   sigdots_block_kernel — sigdots for block-diagonal N
 //
+// Host side (end of the file; declarations in launchers.h): one
+// extern "C" launcher per kernel, and two for the solve, each taking an
+// `int prods` — launch_trsm (trsm_fp_kernel, trsm_fp_rl_kernel) over
+// launch_one_draw<PRODS>, launch_trsm_draws (trsm_fp_draws_kernel) over
+// launch_draws<PRODS>.
+//
 // Each launcher below is one dispatch: there are no environment-
 // selected variants.  The alternatives that were tried and measured
 // neutral or slower (LDS-resident and wave-level solves, a
@@ -60,6 +66,8 @@
 #include <math.h>
 
 #include <algorithm>
+
+#include "launchers.h"
 
 #define FASTFP_MAXMP 128
 #define NB 16  // Cholesky/TRSM block size (one MFMA tile)
@@ -1378,10 +1386,47 @@ static int launch_draws(const double* L, const double* invd,
   return (int)hipGetLastError();
 }
 
+// Launch the one-draw-per-workgroup solve over (ftiles, D, P) in either
+// mode.  PRODS = false accumulates Fp into out (P,D,F) and covers
+// mp <= 256; PRODS = true stores the five products into out (P,D,5,F)
+// and has mp <= 128 only.
+template <bool PRODS>
+static int launch_one_draw(const double* L, const double* invd,
+                           const double* RHS, const double* sNs,
+                           const double* sNr, int mp, int F, int D, int P,
+                           double gsign, double* out, hipStream_t stream) {
+  const int ftiles = (F + FPT_FREQS - 1) / FPT_FREQS;
+  const dim3 grid(ftiles, D, P), blk(512);
+  // the right-looking kernel below has no products mode
+  if (PRODS && mp > FASTFP_MAXMP) return (int)hipErrorInvalidValue;
+  switch (mp >> 4) {
+#define TRSM_CASE(NBT) \
+    case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1, PRODS>), grid, blk, \
+                  0, stream, L, invd, RHS, sNs, sNr, F, D, gsign, out); break;
+    TRSM_CASE(1) TRSM_CASE(2) TRSM_CASE(3) TRSM_CASE(4)
+    TRSM_CASE(5) TRSM_CASE(6) TRSM_CASE(7) TRSM_CASE(8)
+#undef TRSM_CASE
+    // m > 128 (GP-ECORR direct path) dispatches the RIGHT-LOOKING
+    // variant: its single in-place accumulator set (no acc/acc2
+    // chains) keeps W = NBT*4 f64 regs per lane within budget at
+    // NBT up to 16.  The FACTOR for these sizes comes from rocSOLVER
+    // (chol_batch's LDS-resident Sigma caps at 128) + diag_inv.
+#define TRSM_BIG_CASE(NBT) \
+    case NBT: hipLaunchKernelGGL((trsm_fp_rl_kernel<NBT>), grid, blk, 0, \
+                  stream, L, invd, RHS, sNs, sNr, F, D, gsign, out); break;
+    TRSM_BIG_CASE(9) TRSM_BIG_CASE(10) TRSM_BIG_CASE(11) TRSM_BIG_CASE(12)
+    TRSM_BIG_CASE(13) TRSM_BIG_CASE(14) TRSM_BIG_CASE(15) TRSM_BIG_CASE(16)
+#undef TRSM_BIG_CASE
+    default: return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
+}
+
 // ---------------------------------------------------------------------
-// host-side launchers (called from bindings.cpp).  Each returns the
-// hipError_t of its launch as an int (0 = success); a solve dimension
-// with no instantiation is hipErrorInvalidValue, never a silent no-op.
+// host-side launchers (called from bindings.cpp), declared in
+// launchers.h.  Each returns the hipError_t of its launch as an int
+// (0 = success); a solve dimension with no instantiation is
+// hipErrorInvalidValue, never a silent no-op.
 // ---------------------------------------------------------------------
 extern "C" {
 
@@ -1425,80 +1470,35 @@ int launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
   return (int)hipGetLastError();
 }
 
-int launch_trsm_fp(const double* L, const double* invd, const double* RHS,
-                   const double* sNs, const double* sNr, int mp, int F,
-                   int D, int P, double gsign, double* fp,
-                   hipStream_t stream) {
-  const int ftiles = (F + FPT_FREQS - 1) / FPT_FREQS;
-  const dim3 grid(ftiles, D, P), blk(512);
-  switch (mp >> 4) {
-#define TRSM_CASE(NBT) \
-    case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1>), grid, blk, 0, \
-                  stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
-    TRSM_CASE(1) TRSM_CASE(2) TRSM_CASE(3) TRSM_CASE(4)
-    TRSM_CASE(5) TRSM_CASE(6) TRSM_CASE(7) TRSM_CASE(8)
-#undef TRSM_CASE
-    // m > 128 (GP-ECORR direct path) dispatches the RIGHT-LOOKING
-    // variant: its single in-place accumulator set (no acc/acc2
-    // chains) keeps W = NBT*4 f64 regs per lane within budget at
-    // NBT up to 16.  The FACTOR for these sizes comes from rocSOLVER
-    // (chol_batch's LDS-resident Sigma caps at 128) + diag_inv.
-#define TRSM_BIG_CASE(NBT) \
-    case NBT: hipLaunchKernelGGL((trsm_fp_rl_kernel<NBT>), grid, blk, 0, \
-                  stream, L, invd, RHS, sNs, sNr, F, D, gsign, fp); break;
-    TRSM_BIG_CASE(9) TRSM_BIG_CASE(10) TRSM_BIG_CASE(11) TRSM_BIG_CASE(12)
-    TRSM_BIG_CASE(13) TRSM_BIG_CASE(14) TRSM_BIG_CASE(15) TRSM_BIG_CASE(16)
-#undef TRSM_BIG_CASE
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+// One-draw-per-workgroup solve over (ftiles, D, P): Fp accumulated into
+// out (P,D,F), or the five products stored into out (P,D,5,F).
+int launch_trsm(int prods, const double* L, const double* invd,
+                const double* RHS, const double* sNs, const double* sNr,
+                int mp, int F, int D, int P, double gsign, double* out,
+                hipStream_t stream) {
+  return prods ? launch_one_draw<true>(L, invd, RHS, sNs, sNr, mp, F, D, P,
+                                       gsign, out, stream)
+               : launch_one_draw<false>(L, invd, RHS, sNs, sNr, mp, F, D, P,
+                                        gsign, out, stream);
 }
 
 // frequencies per workgroup tile of the draw-looping solve
 int trsm_fp_draws_tile_freqs() { return DL_FREQS; }
 
-// Draw-looping solve (mp <= 64), plain stores into fp (P,D,F); the
+// Draw-looping solve (mp <= 64), plain stores into out (P,D,F) or, in
+// products mode, (P,D,5,F) — the layout and the bits of launch_trsm; the
 // planning is launch_draws'.
-int launch_trsm_fp_draws(const double* L, const double* invd,
-                         const double* RHS, const double* sNs,
-                         const double* sNr, int mp, int F, int D, int P,
-                         double gsign, double* fp, int draws_per_block,
-                         int ncu, int lead, hipStream_t stream) {
-  return launch_draws<false>(L, invd, RHS, sNs, sNr, mp, F, D, P, gsign, fp,
-                             draws_per_block, ncu, lead, stream);
-}
-
-// Products mode of the draw-looping solve: plain stores into out
-// (P,D,5,F), the layout and the bits of launch_trsm_prods.
-int launch_trsm_prods_draws(const double* L, const double* invd,
-                            const double* RHS, const double* sNs,
-                            const double* sNr, int mp, int F, int D, int P,
-                            double gsign, double* out, int draws_per_block,
-                            int ncu, int lead, hipStream_t stream) {
-  return launch_draws<true>(L, invd, RHS, sNs, sNr, mp, F, D, P, gsign, out,
-                            draws_per_block, ncu, lead, stream);
-}
-
-// Products mode (Fe): one launch over (ftiles, D, P), mp <= 128.
-int launch_trsm_prods(const double* L, const double* invd, const double* RHS,
-                      const double* sNs, const double* sNr, int mp, int F,
-                      int D, int P, double gsign, double* out,
-                      hipStream_t stream) {
-  const int ftiles = (F + FPT_FREQS - 1) / FPT_FREQS;
-  const dim3 blk(512);
-  const dim3 grid(ftiles, D, P);
-  switch (mp >> 4) {
-#define TRSM_PRODS_CASE(NBT) \
-    case NBT: hipLaunchKernelGGL((trsm_fp_kernel<NBT, 1, true>), grid, \
-                  blk, 0, stream, L, invd, RHS, sNs, sNr, F, D, gsign, out); \
-      break;
-    TRSM_PRODS_CASE(1) TRSM_PRODS_CASE(2) TRSM_PRODS_CASE(3)
-    TRSM_PRODS_CASE(4) TRSM_PRODS_CASE(5) TRSM_PRODS_CASE(6)
-    TRSM_PRODS_CASE(7) TRSM_PRODS_CASE(8)
-#undef TRSM_PRODS_CASE
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+int launch_trsm_draws(int prods, const double* L, const double* invd,
+                      const double* RHS, const double* sNs,
+                      const double* sNr, int mp, int F, int D, int P,
+                      double gsign, double* out, int draws_per_block,
+                      int ncu, int lead, hipStream_t stream) {
+  return prods ? launch_draws<true>(L, invd, RHS, sNs, sNr, mp, F, D, P,
+                                    gsign, out, draws_per_block, ncu, lead,
+                                    stream)
+               : launch_draws<false>(L, invd, RHS, sNs, sNr, mp, F, D, P,
+                                     gsign, out, draws_per_block, ncu, lead,
+                                     stream);
 }
 
 int launch_diag_inv(const double* L, int mp, long nblk_total, double* invd,

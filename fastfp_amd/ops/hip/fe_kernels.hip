@@ -36,6 +36,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "launchers.h"
+
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 #define MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
 

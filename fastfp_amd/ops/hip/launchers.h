@@ -1,0 +1,84 @@
+// Host-side launchers of the fastfp_amd HIP kernels: the one declaration
+// that the definitions (fastfp_kernels.hip, fe_kernels.hip) and the
+// caller (bindings.cpp) all include.  extern "C" names are not mangled,
+// so without it a drifted signature would still link; with it a
+// definition that disagrees with its declaration does not compile.
+//
+// Every launcher enqueues on `stream` and returns the hipError_t of its
+// launch as an int (0 = success); a solve dimension with no
+// instantiation is hipErrorInvalidValue, never a silent no-op.  All
+// pointers are device pointers to contiguous fp64 unless typed otherwise.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+extern "C" {
+
+// toas/ninv/nr (ntoa,), freqs (F,) -> sNs (3,F), sNr (2,F)
+int launch_sigdots(const double* toas, const double* ninv, const double* nr,
+                   const double* freqs, int ntoa, int F, double* sNs,
+                   double* sNr, hipStream_t stream);
+
+// sigdots for block-diagonal N: toas/uvec/nr (ntoa,) in block order,
+// beta/offsets/sizes (nblk,) -> sNs (3,F), sNr (2,F)
+int launch_sigdots_block(const double* toas, const double* uvec,
+                         const double* nr, const double* freqs,
+                         const double* beta, const long* offsets,
+                         const long* sizes, int nblk, int ntoa, int F,
+                         double* sNs, double* sNr, hipStream_t stream);
+
+// T (ntoa,m), toas/ninv (ntoa,), freqs (F2/2,) -> out[plane][j][c] for
+// j < mp, c < F2, with row stride ldo and one plane (plane_stride apart)
+// per K split
+int launch_sbgemm(const double* T, const double* toas, const double* ninv,
+                  const double* freqs, int ntoa, int m, int mp, int F2,
+                  double* out, long plane_stride, long ldo, int ksplit,
+                  hipStream_t stream);
+
+// TNT (P,m,m), phiinv (P,D,m) -> L (P*D,mp,mp), invd (P*D,mp/16,16,16);
+// mp = 16..128
+int launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
+                      int D, int P, double* L, double* invd,
+                      hipStream_t stream);
+
+// L (B,mp,mp) -> invd, nblk_total = B * mp/16 inverted diagonal blocks
+int launch_diag_inv(const double* L, int mp, long nblk_total, double* invd,
+                    hipStream_t stream);
+
+// The solve, one draw per workgroup: L (P*D,mp,mp), invd
+// (P*D,mp/16,16,16), RHS (P,mp,2F+1), sNs (P,3,F), sNr (P,2,F).
+// prods = 0: Fp ACCUMULATED into out (P,D,F), mp = 16..256;
+// prods = 1: the five products stored into out (P,D,5,F), mp = 16..128.
+int launch_trsm(int prods, const double* L, const double* invd,
+                const double* RHS, const double* sNs, const double* sNr,
+                int mp, int F, int D, int P, double gsign, double* out,
+                hipStream_t stream);
+
+// The same solve with the loop over draws inside the workgroup, mp =
+// 16..64, plain stores in both modes (out as above).  draws_per_block
+// = 0 sizes the slice of draws from the resident workgroup slots of
+// `ncu` compute units; lead (0, 4, 8 or 12) = leading identity rows of
+// the system whose k-steps are left out.
+int launch_trsm_draws(int prods, const double* L, const double* invd,
+                      const double* RHS, const double* sNs,
+                      const double* sNr, int mp, int F, int D, int P,
+                      double gsign, double* out, int draws_per_block,
+                      int ncu, int lead, hipStream_t stream);
+
+// frequencies per workgroup tile of launch_trsm_draws
+int trsm_fp_draws_tile_freqs();
+
+// largest P of the Fe sky kernels
+int fe_max_pulsars();
+
+// prods (P,D,5,F), ant (nsky,P,2) -> fe (D,nsky,F)
+int launch_fe_assemble(const double* prods, const double* ant, int P, int D,
+                       int F, int nsky, double* fe, hipStream_t stream);
+
+// prods (P,D,5,F), ant (nsky,P,2) -> femax, argmax, nskip (D,F); the
+// caller initialises the three outputs
+int launch_fe_skymax(const double* prods, const double* ant, int P, int D,
+                     int F, int nsky, double* femax, int* argmax, int* nskip,
+                     hipStream_t stream);
+
+}  // extern "C"

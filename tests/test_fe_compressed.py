@@ -372,6 +372,27 @@ def test_ragged_compressed_products_gpu():
 
 
 @pytest.mark.gpu
+def test_ragged_compressed_products_chunked_gpu():
+    """The per-pulsar products across a chunk boundary: array B with
+    compression dropped on pulsar 1, draws in chunks of 16 and 4.  The
+    two compressed pulsars (mp = 64) take trsm_prods_store on the 16 and
+    trsm_prods on the 4, the direct pulsar (mp = 80) trsm_prods on both,
+    and no bit differs from the single chunk."""
+    a = _array("B")
+    eng = a.engine(DEV)
+    eng.blocks[1].comp = None
+    eng._stack_compression()
+    assert eng._comp_stack is None
+    assert [b.comp is not None for b in eng.blocks] == [True, False, True]
+    want = eng.sweep_products_hip(a.phiinvs, draw_chunk=32, compressed=True)
+    calls = _counting(eng)
+    got = eng.sweep_products_hip(a.phiinvs, draw_chunk=16, compressed=True)
+    assert calls == {"store": 2, "prods": 4}, calls
+    assert got.shape == (3, 20, 5, 70)
+    assert torch.equal(got, want)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("name", ["A5", "A9"])
 def test_nmfe_compress_device_matches_cpu(name):
     a = _array(name)
