@@ -19,6 +19,7 @@ __version__ = "0.1.0"
 from fastfp_amd.data import (  # noqa: F401
     PulsarData,
     get_tspan,
+    inject_earth_term_cw,
     load_pulsars,
     make_synthetic_pta,
     save_pulsars,
@@ -37,7 +38,13 @@ from fastfp_amd.model import (  # noqa: F401
 )
 from fastfp_amd.xcy import get_xCy  # noqa: F401
 from fastfp_amd.fpstat import FastFp, compute_Fp  # noqa: F401
-from fastfp_amd.festat import FastFe, NMFe, compute_Fe  # noqa: F401
+from fastfp_amd.festat import (  # noqa: F401
+    FastFe,
+    NMFe,
+    compute_Fe,
+    cw_amplitudes,
+    cw_parameters,
+)
 from fastfp_amd.nmfp import NMFp  # noqa: F401
 from fastfp_amd.engine import FpEngine  # noqa: F401
 

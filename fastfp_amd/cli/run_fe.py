@@ -18,6 +18,12 @@ map: ``{savefile}.max.npy`` (nfreqs,) and ``{savefile}.argmax.npy``
 (indices into ``sky``); ``{savefile}.json`` then holds only the
 ``freqs`` and ``sky`` axes.  ``--assemble device`` runs the sky
 assembly of the map in the HIP kernel (GPU only).
+
+``--amplitudes`` (with ``--skymax``) also writes the maximum-likelihood
+amplitudes at each maximum, ``{savefile}.amps.npy`` (nfreqs, 4) in the
+filter order [F+ sin, F+ cos, Fx sin, Fx cos], and the source parameters
+they imply, ``{savefile}.cwpar.npy`` (nfreqs, 4) = [h0, cosi, psi, phi0]
+(``festat.cw_parameters``).
 """
 
 import argparse
@@ -29,7 +35,7 @@ import numpy as np
 import torch
 
 from fastfp_amd.data import load_pulsars
-from fastfp_amd.festat import FastFe
+from fastfp_amd.festat import FastFe, cw_parameters
 from fastfp_amd.model import get_mats_fp, initialize_pta
 from fastfp_amd.parallel import (
     all_gather_concat,
@@ -37,6 +43,12 @@ from fastfp_amd.parallel import (
     init_distributed,
     shard_slice,
 )
+
+
+def cwpar_array(amps, freqs) -> np.ndarray:
+    """(..., F, 4) amplitudes -> (..., F, 4) = [h0, cosi, psi, phi0]."""
+    par = cw_parameters(amps, f=np.asarray(freqs, dtype=np.float64))
+    return np.stack([par[k] for k in ("h0", "cosi", "psi", "phi0")], axis=-1)
 
 
 def fibonacci_sky(nsky: int) -> list:
@@ -65,7 +77,11 @@ def main(
     gwb_comps=30,
     skymax=False,
     assemble="host",
+    amplitudes=False,
 ):
+    if amplitudes and not skymax:
+        raise ValueError("amplitudes=True needs skymax=True: the amplitudes "
+                         "are those at the sky maximum")
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.INFO)
     logger = logging.getLogger(__name__)
 
@@ -108,7 +124,11 @@ def main(
         # per-rank maximum over its sky shard, then the maximum over
         # ranks (shards are in sky order: the first maximum is the
         # lowest sky index)
-        if local_sky:
+        amp = np.full((nfreqs, 4), np.nan)
+        if local_sky and amplitudes:
+            fm, am, amp = fe.sweep_max(freqs, local_sky, Nvecs, Ts, sigmas,
+                                       device=dev, amplitudes=True)
+        elif local_sky:
             fm, am = fe.sweep_max(freqs, local_sky, Nvecs, Ts, sigmas,
                                   device=dev)
         else:
@@ -121,12 +141,22 @@ def main(
         ams = all_gather_concat(
             torch.as_tensor(am[None], dtype=torch.int64), world, dim=0
         ).numpy()
+        if amplitudes:
+            # each rank's amplitudes at its local maximum; the rank that
+            # holds the global maximum is picked below with ``best``
+            amp_all = all_gather_concat(
+                torch.as_tensor(amp[None], dtype=torch.float64), world, dim=0
+            ).numpy()
         logger.info(f"Fe-statistic wall time: {time.perf_counter() - t0:.4f} s")
         if rank == 0:
             best = np.argmax(fms, axis=0)
             cols = np.arange(nfreqs)
             np.save(f"{savefile}.max.npy", fms[best, cols])
             np.save(f"{savefile}.argmax.npy", ams[best, cols])
+            if amplitudes:
+                amps = amp_all[best, cols]
+                np.save(f"{savefile}.amps.npy", amps)
+                np.save(f"{savefile}.cwpar.npy", cwpar_array(amps, freqs))
             with open(f"{savefile}.json", "w") as f:
                 json.dump({"freqs": [float(x) for x in freqs],
                            "sky": [[t, p] for t, p in sky]}, f)
@@ -174,7 +204,14 @@ def cli():
     parser.add_argument("--assemble", choices=["host", "device"],
                         default="host",
                         help="where the sky assembly of the map runs")
-    main(**vars(parser.parse_args()))
+    parser.add_argument("--amplitudes", action="store_true",
+                        help="with --skymax: also write the maximum-"
+                             "likelihood amplitudes (.amps.npy) and source "
+                             "parameters (.cwpar.npy) at each maximum")
+    args = parser.parse_args()
+    if args.amplitudes and not args.skymax:
+        parser.error("--amplitudes requires --skymax")
+    main(**vars(args))
 
 
 if __name__ == "__main__":

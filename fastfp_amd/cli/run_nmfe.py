@@ -14,6 +14,11 @@ columns stripped); the sky grid mirrors ``run_fe``.  Output:
 runs the sky assembly of the cube in the HIP kernel (GPU only).
 ``--compress`` takes the per-pulsar products from the Schur-compressed
 per-draw systems, as ``run_nmfp`` does for Fp.
+
+``--amplitudes`` (with ``--skymax``) also writes the maximum-likelihood
+amplitudes at each maximum, ``{savefile}.amps.npy`` (nsamples, nfreqs, 4)
+in the filter order [F+ sin, F+ cos, Fx sin, Fx cos], and
+``{savefile}.cwpar.npy`` of the same shape = [h0, cosi, psi, phi0].
 """
 
 import argparse
@@ -25,7 +30,7 @@ import time
 import numpy as np
 import torch
 
-from fastfp_amd.cli.run_fe import fibonacci_sky
+from fastfp_amd.cli.run_fe import cwpar_array, fibonacci_sky
 from fastfp_amd.data import get_tspan, load_pulsars
 from fastfp_amd.engine import FpEngine
 from fastfp_amd.festat import NMFe
@@ -58,7 +63,11 @@ def main(
     skymax=False,
     assemble="host",
     compress=False,
+    amplitudes=False,
 ):
+    if amplitudes and not skymax:
+        raise ValueError("amplitudes=True needs skymax=True: the amplitudes "
+                         "are those at the sky maximum")
     logging.basicConfig(format="%(levelname)s: %(message)s", level=logging.INFO)
     logger = logging.getLogger(__name__)
 
@@ -120,18 +129,20 @@ def main(
                 [c.var_slice for c in pta.rn_containers],
                 [c.get_phiinv(noise) for c in pta.rn_containers],
             )
-    parts, parts_arg = [], []
+    parts, parts_arg, parts_amp = [], [], []
     for lo in range(0, len(my_idx), batch_size):
         sel = my_idx[lo : lo + batch_size]
         samples = {
             p: rns_full[ct, sel] for ct, p in enumerate(pta.params)
         }
         if skymax:
-            fm, am = nm.sweep_max(freqs, sky, samples, Nvecs, Ts,
-                                  device=dev, engine=engine,
-                                  compress=compress)
-            parts.append(fm)
-            parts_arg.append(am)
+            res = nm.sweep_max(freqs, sky, samples, Nvecs, Ts,
+                               device=dev, engine=engine,
+                               compress=compress, amplitudes=amplitudes)
+            parts.append(res[0])
+            parts_arg.append(res[1])
+            if amplitudes:
+                parts_amp.append(res[2])
         else:
             parts.append(nm.sweep(freqs, sky, samples, Nvecs, Ts, device=dev,
                                   engine=engine, assemble=assemble,
@@ -146,6 +157,12 @@ def main(
         full_arg = all_gather_concat(
             torch.as_tensor(local_arg, dtype=torch.int64), world, dim=0
         ).numpy()
+    if amplitudes:
+        local_amp = (np.concatenate(parts_amp, axis=0) if parts_amp
+                     else np.zeros((0, ncwfreqs, 4)))
+        full_amp = all_gather_concat(
+            torch.as_tensor(local_amp, dtype=torch.float64), world, dim=0
+        ).numpy()
     logger.info(
         "Noise marginalized Fe-statistic wall time: "
         f"{time.perf_counter() - t0:.2f} s"
@@ -159,6 +176,13 @@ def main(
             with open(os.path.join(outdir, f"{savefile}.argmax.npy"),
                       "wb") as f:
                 np.save(f, full_arg)
+            if amplitudes:
+                with open(os.path.join(outdir, f"{savefile}.amps.npy"),
+                          "wb") as f:
+                    np.save(f, full_amp)
+                with open(os.path.join(outdir, f"{savefile}.cwpar.npy"),
+                          "wb") as f:
+                    np.save(f, cwpar_array(full_amp, freqs))
         else:
             with open(os.path.join(outdir, f"{savefile}.npy"), "wb") as f:
                 np.save(f, full)
@@ -197,7 +221,14 @@ def cli():
                         help="solve the Schur-compressed per-draw systems "
                              "(variable prior bins only), draw by draw where "
                              "the compression margin allows")
-    main(**vars(parser.parse_args()))
+    parser.add_argument("--amplitudes", action="store_true",
+                        help="with --skymax: also write the maximum-"
+                             "likelihood amplitudes (.amps.npy) and source "
+                             "parameters (.cwpar.npy) at each maximum")
+    args = parser.parse_args()
+    if args.amplitudes and not args.skymax:
+        parser.error("--amplitudes requires --skymax")
+    main(**vars(args))
 
 
 if __name__ == "__main__":

@@ -396,6 +396,43 @@ def make_synthetic_pta(
     return psrs
 
 
+def inject_earth_term_cw(psrs, fgw, gwtheta, gwphi, h0=None, zeta=None,
+                         cosi=0.0, psi=0.0, phi0=0.0) -> np.ndarray:
+    """Add a coherent Earth-term continuous wave to every pulsar's
+    residuals, in place.
+
+    The source sits at sky colatitude ``gwtheta`` / longitude ``gwphi``
+    and radiates at ``fgw``; give exactly one of the strain amplitude
+    ``h0`` and the residual amplitude ``zeta = h0 / (2 pi fgw)``
+    (seconds).  With (F+, Fx) from ``festat.gw_antenna_pattern`` and
+    ``a = festat.cw_amplitudes(zeta, cosi, psi, phi0)``,
+
+        r_p(t) = F+_p (a1 sin + a2 cos) + Fx_p (a3 sin + a4 cos)
+
+    with sin / cos of ``2 pi fgw t`` (docs/DESIGN.md, "Fe amplitudes").
+    Pulsars must carry ``.pos``.  Returns ``a`` (4,), which is what
+    ``FastFe.amplitudes`` estimates at this frequency and sky position.
+    """
+    from fastfp_amd.festat import cw_amplitudes, gw_antenna_pattern
+
+    if (h0 is None) == (zeta is None):
+        raise ValueError("give exactly one of h0 and zeta")
+    if zeta is None:
+        zeta = h0 / (2.0 * np.pi * fgw)
+    a = cw_amplitudes(float(zeta), float(cosi), float(psi), float(phi0))
+    for p in psrs:
+        if p.pos is None:
+            raise ValueError(
+                f"pulsar {p.name} has no sky position (.pos); a coherent "
+                "injection needs one")
+        fplus, fcross = gw_antenna_pattern(p.pos, gwtheta, gwphi)
+        arg = 2.0 * np.pi * fgw * p.toas
+        s, c = np.sin(arg), np.cos(arg)
+        p.residuals = p.residuals + (fplus * (a[0] * s + a[1] * c)
+                                     + fcross * (a[2] * s + a[3] * c))
+    return a
+
+
 def get_tspan(psrs: list) -> float:
     """Max - min TOA over the whole array (parity with
     ``enterprise_extensions.model_utils.get_tspan``, used at

@@ -33,6 +33,13 @@ from the HIP solve (``FpEngine.sweep_products_hip``) and run the sky
 assembly in the MFMA kernels ``ops.fe_assemble`` / ``ops.fe_skymax``;
 ``sweep_max`` returns the statistic maximised over the sky with its
 argmax and never forms the (draws x sky x freqs) cube.
+
+The same solve yields the maximum-likelihood amplitudes ``a = M^-1 N``:
+``sweep_max(amplitudes=True)`` returns them at the sky maximum and
+``FastFe.amplitudes`` at one chosen sky position (``ops.fe_amplitudes``
+on a HIP engine, the host solve otherwise); :func:`cw_amplitudes` and
+:func:`cw_parameters` map between ``a`` and the source parameters
+(zeta or h0, cos iota, psi, phi0) — docs/DESIGN.md section 12.
 """
 
 from __future__ import annotations
@@ -76,11 +83,94 @@ def gw_antenna_pattern(pos, gwtheta: float, gwphi: float):
     return fplus, fcross
 
 
-def _assemble_fe(prods, fplus, fcross, rcond=1e-12):
+def cw_amplitudes(zeta, cosi, psi, phi0):
+    """The four Fe amplitudes of an Earth-term continuous wave.
+
+    Signal model (docs/DESIGN.md, "Fe amplitudes"): with ``Phi(t) = 2 pi
+    f t + phi0``, ``zeta = h0 / (2 pi f)`` and ``c = cosi``,
+
+        r+ = zeta [ (1 + c^2) sin Phi cos 2psi + 2c cos Phi sin 2psi]
+        rx = zeta [-(1 + c^2) sin Phi sin 2psi + 2c cos Phi cos 2psi]
+        r_p = F+_p r+ + Fx_p rx
+            = F+_p (a1 sin + a2 cos) + Fx_p (a3 sin + a4 cos),
+
+    sin / cos of ``2 pi f t`` — the filter order of :class:`FastFe`.
+    The arguments broadcast; returns (..., 4) = [a1, a2, a3, a4].
+    """
+    zeta, cosi, psi, phi0 = np.broadcast_arrays(
+        *(np.asarray(x, dtype=np.float64) for x in (zeta, cosi, psi, phi0)))
+    Ap = zeta * (1.0 + cosi**2)
+    Ac = 2.0 * zeta * cosi
+    c2, s2 = np.cos(2.0 * psi), np.sin(2.0 * psi)
+    cp, sp = np.cos(phi0), np.sin(phi0)
+    return np.stack([
+        Ap * c2 * cp - Ac * s2 * sp,
+        Ap * c2 * sp + Ac * s2 * cp,
+        -Ap * s2 * cp - Ac * c2 * sp,
+        -Ap * s2 * sp + Ac * c2 * cp,
+    ], axis=-1)
+
+
+def cw_parameters(a, f=None) -> dict:
+    """Inverse of :func:`cw_amplitudes`: ``a`` (..., 4) -> dict of
+    ``zeta``, ``cosi``, ``psi``, ``phi0`` arrays of the leading shape,
+    plus ``h0 = 2 pi f zeta`` when the frequency ``f`` (broadcast against
+    the leading shape) is given.
+
+    ``psi`` is returned in [0, pi/2) and ``phi0`` in [0, 2 pi):
+    ``(psi + pi/2, phi0 + pi)`` is the same signal.  At circular
+    polarisation (``|cosi| = 1``) only ``phi0 +- 2 psi`` is determined;
+    the returned pair still reproduces ``a``.
+    """
+    a = np.asarray(a, dtype=np.float64)
+    a1, a2, a3, a4 = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+    S = a1**2 + a2**2 + a3**2 + a4**2  # Ap^2 + Ac^2
+    Dd = a1 * a4 - a2 * a3  # Ap Ac
+    r = np.sqrt(np.maximum(S**2 - 4.0 * Dd**2, 0.0))
+    Ap = np.sqrt(0.5 * (S + r))
+    Ac = np.sign(Dd) * np.sqrt(np.maximum(0.5 * (S - r), 0.0))
+    zeta = 0.5 * (Ap + np.sqrt(np.maximum(Ap**2 - Ac**2, 0.0)))
+    pos = zeta > 0.0
+    cosi = np.where(pos, Ac, 0.0) / np.where(pos, 2.0 * zeta, 1.0)
+    alpha = np.arctan2(a2 - a3, a1 + a4)  # 2 psi + phi0
+    beta = np.arctan2(a2 + a3, a1 - a4)  # phi0 - 2 psi
+    psi = 0.25 * (alpha - beta)
+    phi0 = 0.5 * (alpha + beta)
+    # canonical range: every quarter turn of psi is half a turn of phi0
+    k = np.floor(psi / (0.5 * np.pi))
+    psi = psi - k * (0.5 * np.pi)
+    over = psi >= 0.5 * np.pi  # rounding of a psi just below zero
+    psi = np.where(over, psi - 0.5 * np.pi, psi)
+    k = np.where(over, k + 1.0, k)
+    psi = np.maximum(psi, 0.0)
+    phi0 = np.mod(phi0 - k * np.pi, 2.0 * np.pi)
+    phi0 = np.where(phi0 >= 2.0 * np.pi, 0.0, phi0)
+    out = {"zeta": zeta, "cosi": cosi, "psi": psi, "phi0": phi0}
+    if f is not None:
+        out["h0"] = 2.0 * np.pi * np.asarray(f, dtype=np.float64) * zeta
+    return out
+
+
+def _solve4(M, N, rcond):
+    """``M^-1 N`` for stacked 4x4 systems ``M`` (..., 4, 4) and ``N``
+    (..., 4).  If LAPACK finds any system of the stack singular, every
+    one of them goes through the pseudo-inverse."""
+    try:
+        return np.linalg.solve(M, N[..., None])[..., 0]
+    except np.linalg.LinAlgError:
+        flatM = M.reshape(-1, 4, 4)
+        flatN = N.reshape(-1, 4)
+        return np.stack([np.linalg.pinv(Mi, rcond=rcond) @ Ni
+                         for Mi, Ni in zip(flatM, flatN)]).reshape(N.shape)
+
+
+def _assemble_fe(prods, fplus, fcross, rcond=1e-12, amplitudes=False):
     """Fe(f) from per-pulsar corrected products.
 
     ``prods``: (P, 5, F) array of [ss, cc, sc, sr, cr]; ``fplus`` /
-    ``fcross``: (P,) antenna coefficients.  Returns (F,).
+    ``fcross``: (P,) antenna coefficients.  Returns (F,), or with
+    ``amplitudes`` the pair ``(fe (F,), a (F, 4))`` with the
+    maximum-likelihood amplitudes ``a = M^-1 N``.
 
     M is assembled per frequency from sums over pulsars and solved as
     a 4x4 system; near-degenerate skies (e.g. all pulsars clustered:
@@ -111,12 +201,9 @@ def _assemble_fe(prods, fplus, fcross, rcond=1e-12):
     N = np.stack(
         [w(fplus, sr), w(fplus, cr), w(fcross, sr), w(fcross, cr)], axis=1
     )  # (F, 4)
-    try:
-        x = np.linalg.solve(M, N[:, :, None])[:, :, 0]
-    except np.linalg.LinAlgError:
-        x = np.stack([np.linalg.pinv(Mi, rcond=rcond) @ Ni
-                      for Mi, Ni in zip(M, N)])
-    return 0.5 * np.einsum("fi,fi->f", N, x)
+    x = _solve4(M, N, rcond)
+    fe = 0.5 * np.einsum("fi,fi->f", N, x)
+    return (fe, x) if amplitudes else fe
 
 
 def _check_assemble(assemble, device, engine):
@@ -165,6 +252,25 @@ def _antenna_table(pos, sky, device=None):
     if device is None:
         return ant
     return torch.as_tensor(ant, dtype=torch.float64).to(device)
+
+
+def _host_max_amplitudes(assemble, prods, coeffs):
+    """Host reference of the sky maximum with amplitudes.  ``assemble``
+    is ``_assemble_fe`` or ``_assemble_fe_draws``, ``coeffs`` the (F+,
+    Fx) pair of every sky point.  Returns ``(femax, argmax, amps)`` of
+    the assembly's output shape (+ (4,) for ``amps``); the solve is
+    repeated with amplitudes only at the sky points that hold a
+    maximum."""
+    grid = np.stack([assemble(prods, fplus, fcross)
+                     for fplus, fcross in coeffs])  # (nsky, ...)
+    femax = np.nanmax(grid, axis=0)
+    argmax = np.nanargmax(grid, axis=0)
+    amps = np.empty(argmax.shape + (4,))
+    for k in np.unique(argmax):
+        _, a = assemble(prods, *coeffs[k], amplitudes=True)
+        sel = argmax == k
+        amps[sel] = a[sel]
+    return femax, argmax, amps
 
 
 class FastFe:
@@ -267,6 +373,7 @@ class FastFe:
         sigmas,
         device: str = None,
         engine: FpEngine = None,
+        amplitudes: bool = False,
     ):
         """Fe maximised over ``sky`` per frequency.
 
@@ -276,6 +383,12 @@ class FastFe:
         (F,)-sized results leave the device; on a CPU engine this is the
         host assembly followed by ``np.nanmax`` / ``np.nanargmax`` (the
         reference implementation).
+
+        ``amplitudes``: return ``(femax, argmax, amps (F, 4))`` with the
+        maximum-likelihood amplitudes ``M^-1 N`` at the maximum
+        (:func:`cw_parameters` turns them into source parameters).  On a
+        HIP engine the ``fe_amplitudes`` kernel reads the same device
+        products at ``argmax``; on a CPU engine it is the host solve.
         """
         if device is None:
             device = "cuda" if torch.cuda.is_available() else "cpu"
@@ -287,13 +400,59 @@ class FastFe:
 
             prods = engine.sweep_products_hip(
                 _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
-            femax, argmax, _ = ops.fe_skymax(
-                prods[:, None].contiguous(),
-                _antenna_table(self.pos, sky, engine.device))
-            return (femax[0].cpu().numpy(),
-                    argmax[0].cpu().numpy().astype(np.int64))
+            prods = prods[:, None].contiguous()
+            ant_d = _antenna_table(self.pos, sky, engine.device)
+            femax, argmax, _ = ops.fe_skymax(prods, ant_d)
+            out = (femax[0].cpu().numpy(),
+                   argmax[0].cpu().numpy().astype(np.int64))
+            if amplitudes:
+                amps, _, _ = ops.fe_amplitudes(prods, ant_d, argmax)
+                out += (amps[0].cpu().numpy(),)
+            return out
+        if amplitudes:
+            # the assembly of ``sweep``, call for call
+            prods = engine.sweep_products(sigmas=sigmas).cpu().numpy()
+            return _host_max_amplitudes(
+                _assemble_fe, prods,
+                [gw_antenna_pattern(self.pos, th, ph) for th, ph in sky])
         grid = self.sweep(freqs, sky, Nvecs, Ts, sigmas, engine=engine)
         return np.nanmax(grid, axis=0), np.nanargmax(grid, axis=0)
+
+    def amplitudes(
+        self,
+        freqs,
+        gwtheta,
+        gwphi,
+        Nvecs,
+        Ts,
+        sigmas,
+        device: str = None,
+        engine: FpEngine = None,
+    ):
+        """Targeted search at one sky position: ``(fe (F,), amps (F,
+        4))``, the statistic and the maximum-likelihood amplitudes
+        ``M^-1 N`` per frequency.  HIP engine: products from the HIP
+        solve, ``fe_amplitudes`` kernel; CPU engine: the host solve."""
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        if engine is None:
+            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
+            engine.precompute(freqs)
+        sky = [(float(gwtheta), float(gwphi))]
+        if engine._use_hip:
+            from fastfp_amd import ops
+
+            prods = engine.sweep_products_hip(
+                _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
+            prods = prods[:, None].contiguous()
+            idx = torch.zeros((1, prods.shape[3]), dtype=torch.int32,
+                              device=prods.device)
+            amps, fe, _ = ops.fe_amplitudes(
+                prods, _antenna_table(self.pos, sky, engine.device), idx)
+            return fe[0].cpu().numpy(), amps[0].cpu().numpy()
+        prods = engine.sweep_products(sigmas=sigmas).cpu().numpy()
+        fplus, fcross = gw_antenna_pattern(self.pos, *sky[0])
+        return _assemble_fe(prods, fplus, fcross, amplitudes=True)
 
 
 def compute_Fe(psrs, pta, noise, freqs, sky, device=None) -> np.ndarray:
@@ -305,8 +464,9 @@ def compute_Fe(psrs, pta, noise, freqs, sky, device=None) -> np.ndarray:
                                    device=device)
 
 
-def _assemble_fe_draws(prods, fplus, fcross, rcond=1e-12):
-    """Draw-batched Fe assembly: ``prods`` (P, D, 5, F) -> (D, F)."""
+def _assemble_fe_draws(prods, fplus, fcross, rcond=1e-12, amplitudes=False):
+    """Draw-batched Fe assembly: ``prods`` (P, D, 5, F) -> (D, F), or
+    with ``amplitudes`` -> ``(fe (D, F), a (D, F, 4))``."""
     ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
     sr, cr = prods[:, :, 3], prods[:, :, 4]
     fp2, fx2, fpx = fplus**2, fcross**2, fplus * fcross
@@ -329,14 +489,9 @@ def _assemble_fe_draws(prods, fplus, fcross, rcond=1e-12):
     N = np.stack(
         [w(fplus, sr), w(fplus, cr), w(fcross, sr), w(fcross, cr)], axis=-1
     )  # (D, F, 4)
-    try:
-        x = np.linalg.solve(M, N[..., None])[..., 0]
-    except np.linalg.LinAlgError:
-        flatM = M.reshape(-1, 4, 4)
-        flatN = N.reshape(-1, 4)
-        x = np.stack([np.linalg.pinv(Mi, rcond=rcond) @ Ni
-                      for Mi, Ni in zip(flatM, flatN)]).reshape(D, F, 4)
-    return 0.5 * np.einsum("dfi,dfi->df", N, x)
+    x = _solve4(M, N, rcond)
+    fe = 0.5 * np.einsum("dfi,dfi->df", N, x)
+    return (fe, x) if amplitudes else fe
 
 
 class NMFe:
@@ -456,6 +611,7 @@ class NMFe:
         draw_chunk: int = 128,
         engine: FpEngine = None,
         compress: bool = False,
+        amplitudes: bool = False,
     ):
         """Fe maximised over ``sky`` for every (draw, frequency).
 
@@ -466,6 +622,10 @@ class NMFe:
         device; on a CPU engine each chunk is assembled on the host and
         reduced with ``np.nanmax`` / ``np.nanargmax`` (the reference
         implementation).  ``compress``: as in :meth:`sweep`.
+
+        ``amplitudes``: return ``(femax, argmax, amps (D, F, 4))`` with
+        the maximum-likelihood amplitudes at each maximum, as in
+        :meth:`FastFe.sweep_max`.
         """
         from fastfp_amd.noise import batch_phiinv
 
@@ -479,6 +639,7 @@ class NMFe:
         F = engine.freqs.shape[0]
         femax = np.empty((D, F))
         argmax = np.empty((D, F), dtype=np.int64)
+        amps = np.empty((D, F, 4)) if amplitudes else None
         if engine._use_hip:
             from fastfp_amd import ops
 
@@ -494,6 +655,17 @@ class NMFe:
                 fm, am, _ = ops.fe_skymax(prods, ant_d)
                 femax[lo:hi] = fm.cpu().numpy()
                 argmax[lo:hi] = am.cpu().numpy()
+                if amplitudes:
+                    amps[lo:hi] = ops.fe_amplitudes(
+                        prods, ant_d, am)[0].cpu().numpy()
+            elif amplitudes:
+                prods = self._products(engine, chunk, compress,
+                                       hip=False).cpu().numpy()
+                femax[lo:hi], argmax[lo:hi], amps[lo:hi] = \
+                    _host_max_amplitudes(
+                        _assemble_fe_draws, prods,
+                        [(ant[k, :, 0], ant[k, :, 1])
+                         for k in range(len(sky))])
             else:
                 prods = self._products(engine, chunk, compress,
                                        hip=False).cpu().numpy()
@@ -503,4 +675,6 @@ class NMFe:
                 ])  # (nsky, Dc, F)
                 femax[lo:hi] = np.nanmax(cube, axis=0)
                 argmax[lo:hi] = np.nanargmax(cube, axis=0)
+        if amplitudes:
+            return femax, argmax, amps
         return femax, argmax

@@ -271,3 +271,50 @@ def fe_skymax(prods, ant, repair: bool = True):
         argmax[d_idx, f_idx] = torch.as_tensor(
             np.nanargmax(vals, axis=0), dtype=argmax.dtype).to(argmax.device)
     return femax, argmax, nskip
+
+
+def fe_amplitudes(prods, ant, idx, repair: bool = True):
+    """Maximum-likelihood Fe amplitudes ``a = M^-1 N`` at one sky index
+    per (draw, frequency) column, on the device: the products and the
+    antenna table stay where ``fe_skymax`` read them.
+
+    ``prods`` (P, D, 5, F) and ``ant`` (nsky, P, 2) as in
+    :func:`fe_assemble` (any P >= 1: this kernel keeps no LDS tile);
+    ``idx`` (D, F) integer rows of ``ant``, e.g. the ``argmax`` of
+    :func:`fe_skymax`.  Returns ``(amps (D, F, 4) f64, fe (D, F) f64,
+    status (D, F) int32)`` device tensors.  ``status`` 0: solved; 1: a
+    degenerate or non-finite Cholesky pivot (the rule of the sky
+    kernels); 2: ``idx`` outside ``[0, nsky)``.  ``amps`` and ``fe`` are
+    NaN where ``status`` is not 0.
+
+    With ``repair`` the status-1 columns are recomputed on the host
+    through ``festat._assemble_fe_draws`` (pseudo-inverse branch) and
+    come back finite; ``status`` keeps the kernel's values.  The common
+    path costs one ``.any()`` sync.
+    """
+    ext = _fe_ext()
+    idx = idx.to(device=prods.device, dtype=torch.int32).contiguous()
+    amps, fe, status = ext.fe_amplitudes(
+        prods.contiguous(), ant.contiguous(), idx)
+    if not repair:
+        return amps, fe, status
+    bad = status == 1
+    if bool(bad.any()):
+        from fastfp_amd.festat import _assemble_fe_draws
+
+        d_idx, f_idx = torch.nonzero(bad, as_tuple=True)
+        rows = idx[d_idx, f_idx]
+        for k in torch.unique(rows).tolist():
+            sel = rows == k
+            dk, fk = d_idx[sel], f_idx[sel]
+            # this sky row's bad columns as a (P, ncols, 5, 1) product set
+            sub_h = prods[:, dk, :, fk].permute(1, 0, 2).unsqueeze(-1)
+            ant_h = ant[k].cpu().numpy()
+            fe_h, a_h = _assemble_fe_draws(
+                sub_h.cpu().numpy(), ant_h[:, 0], ant_h[:, 1],
+                amplitudes=True)
+            fe[dk, fk] = torch.as_tensor(
+                fe_h[:, 0], dtype=fe.dtype).to(fe.device)
+            amps[dk, fk] = torch.as_tensor(
+                a_h[:, 0], dtype=amps.dtype).to(amps.device)
+    return amps, fe, status

@@ -276,7 +276,8 @@ void trsm_prods_store(torch::Tensor L, torch::Tensor invd, torch::Tensor RHS,
 
 namespace {
 
-void check_fe_inputs(const torch::Tensor& prods, const torch::Tensor& ant) {
+// dtype, shape and device checks common to every Fe kernel
+void check_fe_shapes(const torch::Tensor& prods, const torch::Tensor& ant) {
   check_f64(prods, "prods");
   check_f64(ant, "ant");
   TORCH_CHECK(prods.dim() == 4 && prods.size(2) == 5,
@@ -285,16 +286,57 @@ void check_fe_inputs(const torch::Tensor& prods, const torch::Tensor& ant) {
                   ant.size(1) == prods.size(0),
               "ant must be (nsky, P, 2) with P matching prods");
   TORCH_CHECK(ant.device() == prods.device(), "prods/ant device mismatch");
-  TORCH_CHECK(prods.size(0) >= 1 && prods.size(0) <= fe_max_pulsars(),
-              "the Fe sky kernels keep a (5, P, 16) product tile in LDS and "
-              "support 1 <= P <= ", fe_max_pulsars(), " pulsars; got P=",
-              prods.size(0));
+}
+
+void check_fe_dims(const torch::Tensor& prods, const torch::Tensor& ant) {
   TORCH_CHECK(prods.size(3) < (1L << 31) && ant.size(0) < (1L << 31) &&
                   prods.size(1) < (1L << 31),
               "dimension overflow");
 }
 
+void check_fe_inputs(const torch::Tensor& prods, const torch::Tensor& ant) {
+  check_fe_shapes(prods, ant);
+  TORCH_CHECK(prods.size(0) >= 1 && prods.size(0) <= fe_max_pulsars(),
+              "the Fe sky kernels keep a (5, P, 16) product tile in LDS and "
+              "support 1 <= P <= ", fe_max_pulsars(), " pulsars; got P=",
+              prods.size(0));
+  check_fe_dims(prods, ant);
+}
+
 }  // namespace
+
+// fe_amplitudes: the 4x4 solve at ONE sky row idx (D,F) i32 per column ->
+// amps (D,F,4) = M^-1 N, fe (D,F), status (D,F) i32: 0 solved, 1
+// degenerate pivot, 2 idx outside [0, nsky); NaN where status != 0.  No
+// pulsar cap: the kernel keeps no product tile.
+std::vector<torch::Tensor> fe_amplitudes(torch::Tensor prods,
+                                         torch::Tensor ant,
+                                         torch::Tensor idx) {
+  check_fe_shapes(prods, ant);
+  TORCH_CHECK(prods.size(0) >= 1 && prods.size(0) < (1L << 31),
+              "fe_amplitudes needs P >= 1 pulsars; got P=", prods.size(0));
+  check_fe_dims(prods, ant);
+  TORCH_CHECK(idx.is_cuda() && idx.device() == prods.device(),
+              "idx must be on the device of prods");
+  TORCH_CHECK(idx.scalar_type() == torch::kInt32, "idx must be int32");
+  TORCH_CHECK(idx.is_contiguous(), "idx must be contiguous");
+  TORCH_CHECK(idx.dim() == 2 && idx.size(0) == prods.size(1) &&
+                  idx.size(1) == prods.size(3),
+              "idx must be (D, F) matching prods");
+  const int P = prods.size(0), D = prods.size(1), F = prods.size(3);
+  const int nsky = ant.size(0);
+  auto iopts = prods.options().dtype(torch::kInt32);
+  auto amps = torch::empty({D, F, 4}, prods.options());
+  auto fe = torch::empty({D, F}, prods.options());
+  auto status = torch::empty({D, F}, iopts);
+  check_launch(
+      launch_fe_amplitudes(prods.data_ptr<double>(), ant.data_ptr<double>(),
+                           idx.data_ptr<int>(), P, D, F, nsky,
+                           amps.data_ptr<double>(), fe.data_ptr<double>(),
+                           status.data_ptr<int>(), stream()),
+      "fe_amplitudes");
+  return {amps, fe, status};
+}
 
 // fe_assemble: prods (P,D,5,F), ant (nsky,P,2) -> fe (D,nsky,F); NaN at
 // points whose 4x4 M has a degenerate Cholesky pivot.
@@ -407,4 +449,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fe sky assembly: MFMA pulsar sums + in-register 4x4 solve");
   m.def("fe_skymax", &fe_skymax,
         "Fe sky assembly fused with the maximum over sky points");
+  m.def("fe_amplitudes", &fe_amplitudes,
+        "Fe maximum-likelihood amplitudes at one sky index per column");
 }

@@ -267,6 +267,128 @@ __global__ __launch_bounds__(FE_THREADS, 3) void fe_sky_kernel(
   }
 }
 
+// fe_point with the back substitution: the same LDL^T and forward solve,
+// operation for operation (kept apart from fe_point so the sky kernels
+// compile exactly as before), then a = L^-T D^-1 z.  a[0..3] multiply
+// the filters F+ sin, F+ cos, Fx sin, Fx cos.
+static __device__ __forceinline__ bool fe_point_amps(const double* s,
+                                                     double* fe, double* a) {
+  const double m00 = s[S_P2SS], m01 = s[S_P2SC], m02 = s[S_PXSS];
+  const double m03 = s[S_PXSC], m11 = s[S_P2CC], m12 = s[S_PXSC];
+  const double m13 = s[S_PXCC], m22 = s[S_X2SS], m23 = s[S_X2SC];
+  const double m33 = s[S_X2CC];
+
+  const double d0 = m00;
+  if (!fe_pivot_ok(d0, m00)) return false;
+  const double i0 = 1.0 / d0;
+  const double l10 = m01 * i0, l20 = m02 * i0, l30 = m03 * i0;
+
+  const double d1 = fma(-l10, m01, m11);
+  if (!fe_pivot_ok(d1, m11)) return false;
+  const double i1 = 1.0 / d1;
+  const double t21 = fma(-l20, m01, m12);
+  const double t31 = fma(-l30, m01, m13);
+  const double l21 = t21 * i1, l31 = t31 * i1;
+
+  const double d2 = fma(-l21, t21, fma(-l20, m02, m22));
+  if (!fe_pivot_ok(d2, m22)) return false;
+  const double i2 = 1.0 / d2;
+  const double t32 = fma(-l31, t21, fma(-l30, m02, m23));
+  const double l32 = t32 * i2;
+
+  const double d3 = fma(-l32, t32, fma(-l31, t31, fma(-l30, m03, m33)));
+  if (!fe_pivot_ok(d3, m33)) return false;
+  const double i3 = 1.0 / d3;
+
+  const double z0 = s[S_PSR];
+  const double z1 = fma(-l10, z0, s[S_PCR]);
+  const double z2 = fma(-l21, z1, fma(-l20, z0, s[S_XSR]));
+  const double z3 = fma(-l32, z2, fma(-l31, z1, fma(-l30, z0, s[S_XCR])));
+  *fe = 0.5 * fma(z3 * z3, i3, fma(z2 * z2, i2, fma(z1 * z1, i1, z0 * z0 * i0)));
+
+  // L^T a = D^-1 z, from the last row up
+  const double a3 = z3 * i3;
+  const double a2 = fma(-l32, a3, z2 * i2);
+  const double a1 = fma(-l31, a3, fma(-l21, a2, z1 * i1));
+  const double a0 = fma(-l30, a3, fma(-l20, a2, fma(-l10, a1, z0 * i0)));
+  a[0] = a0;
+  a[1] = a1;
+  a[2] = a2;
+  a[3] = a3;
+  return true;
+}
+
+#define FE_AMPS_THREADS 64
+
+// Maximum-likelihood amplitudes a = M^-1 N at ONE sky index per column.
+// grid = ceil(D*F / 64);  block = 64: one thread per column n = d*F + f,
+// so the five product loads of a k-step are contiguous in f across
+// lanes.  The 13 sums run as a serial k = 0..P-1 FMA chain (fixed order:
+// bitwise reproducible); the antenna pair comes from row idx[n] of the
+// L2-resident table.  No LDS, no barriers, no atomics, no cap on P.
+// status: 0 solved; 1 degenerate or non-finite pivot (fe_pivot_ok);
+// 2 idx[n] outside [0, nsky) — the antenna table is not read.  amps and
+// fe are NaN wherever status != 0.
+__global__ __launch_bounds__(FE_AMPS_THREADS) void fe_amps_kernel(
+    const double* __restrict__ prods /*(P, D, 5, F)*/,
+    const double* __restrict__ ant /*(nsky, P, 2)*/,
+    const int* __restrict__ idx /*(D, F)*/, int P, int D, int F, int nsky,
+    double* __restrict__ amps /*(D, F, 4)*/, double* __restrict__ fe /*(D, F)*/,
+    int* __restrict__ status /*(D, F)*/) {
+  const long NC = (long)D * F;
+  const long n = (long)blockIdx.x * FE_AMPS_THREADS + threadIdx.x;
+  if (n >= NC) return;
+  const long d = n / F;
+  const long f = n - d * F;
+  const int row = idx[n];
+
+  double a[4] = {NAN, NAN, NAN, NAN};
+  double val = NAN;
+  int st = 2;
+  if (row >= 0 && row < nsky) {
+    const double* ap = ant + (long)row * P * 2;
+    const double* pp = prods + d * 5 * F + f;
+    const long pstride = (long)D * 5 * F;
+    double s[FE_NSUM];
+#pragma unroll
+    for (int i = 0; i < FE_NSUM; ++i) s[i] = 0.0;
+    for (int k = 0; k < P; ++k) {
+      const double fp = ap[2 * k], fx = ap[2 * k + 1];
+      const double* q = pp + (long)k * pstride;
+      const double bss = q[0], bcc = q[F], bsc = q[2 * (long)F];
+      const double bsr = q[3 * (long)F], bcr = q[4 * (long)F];
+      const double p2 = fp * fp, px = fp * fx, x2 = fx * fx;
+      s[S_P2SS] = fma(p2, bss, s[S_P2SS]);
+      s[S_P2SC] = fma(p2, bsc, s[S_P2SC]);
+      s[S_P2CC] = fma(p2, bcc, s[S_P2CC]);
+      s[S_PXSS] = fma(px, bss, s[S_PXSS]);
+      s[S_PXSC] = fma(px, bsc, s[S_PXSC]);
+      s[S_PXCC] = fma(px, bcc, s[S_PXCC]);
+      s[S_X2SS] = fma(x2, bss, s[S_X2SS]);
+      s[S_X2SC] = fma(x2, bsc, s[S_X2SC]);
+      s[S_X2CC] = fma(x2, bcc, s[S_X2CC]);
+      s[S_PSR] = fma(fp, bsr, s[S_PSR]);
+      s[S_PCR] = fma(fp, bcr, s[S_PCR]);
+      s[S_XSR] = fma(fx, bsr, s[S_XSR]);
+      s[S_XCR] = fma(fx, bcr, s[S_XCR]);
+    }
+    double v = 0.0, x[4];
+    const bool ok = fe_point_amps(s, &v, x) && (fabs(v) < INFINITY) &&
+                    (fabs(x[0]) < INFINITY) && (fabs(x[1]) < INFINITY) &&
+                    (fabs(x[2]) < INFINITY) && (fabs(x[3]) < INFINITY);
+    st = ok ? 0 : 1;
+    if (ok) {
+      val = v;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = x[i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) amps[4 * n + i] = a[i];
+  fe[n] = val;
+  status[n] = st;
+}
+
 extern "C" {
 
 // Largest P the resident product tile supports: 5 * Kp * 16 doubles of
@@ -310,6 +432,20 @@ int launch_fe_skymax(const double* prods, const double* ant, int P, int D,
                      hipStream_t stream) {
   return (int)fe_launch_common(true, prods, ant, P, D, F, nsky, nullptr,
                                femax, argmax, nskip, stream);
+}
+
+int launch_fe_amplitudes(const double* prods, const double* ant,
+                         const int* idx, int P, int D, int F, int nsky,
+                         double* amps, double* fe, int* status,
+                         hipStream_t stream) {
+  const long NC = (long)D * F;
+  if (NC == 0) return (int)hipSuccess;
+  const long nblk = (NC + FE_AMPS_THREADS - 1) / FE_AMPS_THREADS;
+  if (nblk > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(fe_amps_kernel, dim3((unsigned)nblk),
+                     dim3(FE_AMPS_THREADS), 0, stream, prods, ant, idx, P, D,
+                     F, nsky, amps, fe, status);
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -81,4 +81,12 @@ int launch_fe_skymax(const double* prods, const double* ant, int P, int D,
                      int F, int nsky, double* femax, int* argmax, int* nskip,
                      hipStream_t stream);
 
+// prods (P,D,5,F), ant (nsky,P,2), idx (D,F) sky row per column -> amps
+// (D,F,4) = M^-1 N, fe (D,F), status (D,F): 0 solved, 1 degenerate pivot,
+// 2 idx outside [0, nsky); NaN where status != 0.  Any P >= 1.
+int launch_fe_amplitudes(const double* prods, const double* ant,
+                         const int* idx, int P, int D, int F, int nsky,
+                         double* amps, double* fe, int* status,
+                         hipStream_t stream);
+
 }  // extern "C"

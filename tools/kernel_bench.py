@@ -17,7 +17,8 @@ same system padded in front, with lead = 0 and with the skipped k-steps.
 times the factor kernel alone (chol_batch_into) at the stacked shape;
 defaults P=67, D=1024, m=60 (mp = 64).
 
-times the Fe-on-device kernels (trsm_prods, fe_assemble, fe_skymax);
+times the Fe-on-device kernels (trsm_prods, fe_assemble, fe_skymax,
+fe_amplitudes at the argmax);
 defaults P=67, D=256, F=200, nsky=768, m=120.  It also times the
 products solve at the compressed shape (m / 2 variable columns padded in
 front to mp, gsign = -1): trsm_prods and trsm_prods_store on the same
@@ -286,6 +287,17 @@ def main_fe(P=67, D=256, F=200, nsky=768, m=120):
     assert torch.equal(femax, fmap.max(dim=1).values)
     print(f"check: nskip=0, skymax == max(map) bitwise; "
           f"femax range [{float(femax.min()):.3g}, {float(femax.max()):.3g}]")
+    # the amplitudes at the maximum: one sky row per column, 1/nsky of
+    # the sky pass; reads all of prods once
+    t = timeit(lambda: ext.fe_amplitudes(prods, ant, argmax), iters=50,
+               warmup=5)
+    nbytes = prods.numel() * 8
+    print(f"fe_amplitudes D*F={D*F}: {t*1e3:9.3f} ms"
+          f"  ({nbytes/t/1e9:7.1f} GB/s product read)")
+    amps, fe_a, status = ext.fe_amplitudes(prods, ant, argmax)
+    assert int(status.sum()) == 0, "bench inputs must be non-degenerate"
+    rel = float(((fe_a - femax).abs() / femax).max())
+    print(f"check: status=0, fe at argmax vs femax max rel diff {rel:.2e}")
 
 
 if __name__ == "__main__":
