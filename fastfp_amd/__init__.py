@@ -5,7 +5,8 @@ Brand-new implementation of the capabilities of ``gabefreedman/fastfp``
 PyTorch-ROCm fp64 tensors, hand-written HIP/CDNA4 kernels (MFMA fp64
 DGEMM, batched Cholesky, fused triangular-solve + 2x2 Fp reduction,
 Fe sky assembly with a fused maximum over the sky — ``FastFe.sweep_max``
-/ ``NMFe.sweep_max``) and
+/ ``NMFe.sweep_max``, and the Monte-Carlo null of that maximum —
+``FastFe.null_max`` / ``FastFe.false_alarm`` / ``NMFe.null_max``) and
 ``torch.distributed``/RCCL draw- and frequency-sharding over xGMI.
 No JAX, no Triton, no CUDA-compat shims.
 
@@ -44,6 +45,7 @@ from fastfp_amd.festat import (  # noqa: F401
     compute_Fe,
     cw_amplitudes,
     cw_parameters,
+    false_alarm_probability,
 )
 from fastfp_amd.nmfp import NMFp  # noqa: F401
 from fastfp_amd.engine import FpEngine  # noqa: F401

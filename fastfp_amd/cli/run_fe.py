@@ -24,6 +24,15 @@ amplitudes at each maximum, ``{savefile}.amps.npy`` (nfreqs, 4) in the
 filter order [F+ sin, F+ cos, Fx sin, Fx cos], and the source parameters
 they imply, ``{savefile}.cwpar.npy`` (nfreqs, 4) = [h0, cosi, psi, phi0]
 (``festat.cw_parameters``).
+
+``--null R`` (with ``--skymax``) also draws ``R`` noise-only realisations
+of the sky maximum per frequency (``FastFe.null_max``, seed
+``--null_seed``) and writes ``{savefile}.null.npy`` (R, nfreqs) and the
+false-alarm probability of each observed maximum,
+``{savefile}.pfa.npy`` (nfreqs,) = (1 + #{null >= max}) / (1 + R).  The
+normals do not depend on the sky, so under torchrun every rank draws the
+same ones and takes the null maximum over its sky shard; the elementwise
+maximum over ranks is the single-process null.
 """
 
 import argparse
@@ -35,7 +44,8 @@ import numpy as np
 import torch
 
 from fastfp_amd.data import load_pulsars
-from fastfp_amd.festat import FastFe, cw_parameters
+from fastfp_amd.engine import FpEngine
+from fastfp_amd.festat import FastFe, cw_parameters, false_alarm_probability
 from fastfp_amd.model import get_mats_fp, initialize_pta
 from fastfp_amd.parallel import (
     all_gather_concat,
@@ -78,7 +88,14 @@ def main(
     skymax=False,
     assemble="host",
     amplitudes=False,
+    null=0,
+    null_seed=0,
 ):
+    if null and not skymax:
+        raise ValueError("null needs skymax=True: the null distribution is "
+                         "that of the sky maximum")
+    if null < 0:
+        raise ValueError("null must be a number of realisations >= 0")
     if amplitudes and not skymax:
         raise ValueError("amplitudes=True needs skymax=True: the amplitudes "
                          "are those at the sky maximum")
@@ -125,12 +142,18 @@ def main(
         # ranks (shards are in sky order: the first maximum is the
         # lowest sky index)
         amp = np.full((nfreqs, 4), np.nan)
+        engine = None
+        if local_sky and null:
+            # one precompute serves the observed pass and the null pass
+            engine = FpEngine(psrs, Nvecs, Ts, device=dev)
+            engine.precompute(freqs)
         if local_sky and amplitudes:
             fm, am, amp = fe.sweep_max(freqs, local_sky, Nvecs, Ts, sigmas,
-                                       device=dev, amplitudes=True)
+                                       device=dev, engine=engine,
+                                       amplitudes=True)
         elif local_sky:
             fm, am = fe.sweep_max(freqs, local_sky, Nvecs, Ts, sigmas,
-                                  device=dev)
+                                  device=dev, engine=engine)
         else:
             fm = np.full(nfreqs, -np.inf)
             am = np.zeros(nfreqs, dtype=np.int64)
@@ -147,6 +170,15 @@ def main(
             amp_all = all_gather_concat(
                 torch.as_tensor(amp[None], dtype=torch.float64), world, dim=0
             ).numpy()
+        if null:
+            # every rank draws the same normals (they do not depend on the
+            # sky); the maximum over its shard, then over ranks
+            nl = (fe.null_max(freqs, local_sky, Nvecs, Ts, sigmas, null,
+                              seed=null_seed, engine=engine)
+                  if local_sky else np.full((null, nfreqs), -np.inf))
+            nls = all_gather_concat(
+                torch.as_tensor(nl[None], dtype=torch.float64), world, dim=0
+            ).numpy().max(axis=0)
         logger.info(f"Fe-statistic wall time: {time.perf_counter() - t0:.4f} s")
         if rank == 0:
             best = np.argmax(fms, axis=0)
@@ -157,6 +189,10 @@ def main(
                 amps = amp_all[best, cols]
                 np.save(f"{savefile}.amps.npy", amps)
                 np.save(f"{savefile}.cwpar.npy", cwpar_array(amps, freqs))
+            if null:
+                np.save(f"{savefile}.null.npy", nls)
+                np.save(f"{savefile}.pfa.npy",
+                        false_alarm_probability(fms[best, cols], nls))
             with open(f"{savefile}.json", "w") as f:
                 json.dump({"freqs": [float(x) for x in freqs],
                            "sky": [[t, p] for t, p in sky]}, f)
@@ -208,7 +244,16 @@ def cli():
                         help="with --skymax: also write the maximum-"
                              "likelihood amplitudes (.amps.npy) and source "
                              "parameters (.cwpar.npy) at each maximum")
+    parser.add_argument("--null", type=int, default=0, metavar="R",
+                        help="with --skymax: also draw R noise-only "
+                             "realisations of the sky maximum (.null.npy) "
+                             "and write the false-alarm probability of each "
+                             "observed maximum (.pfa.npy)")
+    parser.add_argument("--null_seed", type=int, default=0,
+                        help="seed of the --null realisations")
     args = parser.parse_args()
+    if args.null and not args.skymax:
+        parser.error("--null requires --skymax")
     if args.amplitudes and not args.skymax:
         parser.error("--amplitudes requires --skymax")
     main(**vars(args))

@@ -40,6 +40,14 @@ The same solve yields the maximum-likelihood amplitudes ``a = M^-1 N``:
 on a HIP engine, the host solve otherwise); :func:`cw_amplitudes` and
 :func:`cw_parameters` map between ``a`` and the source parameters
 (zeta or h0, cos iota, psi, phi0) — docs/DESIGN.md section 12.
+
+Significance of the sky maximum: ``FastFe.null_max`` / ``NMFe.null_max``
+draw the maximum under noise alone and ``FastFe.false_alarm`` turns the
+observed maximum into a false-alarm probability, without a solve per
+realisation — for ``r ~ N(0, C)`` the data products of a pulsar are
+exactly ``(sr, cr) ~ N(0, [[ss, sc], [sc, cc]])`` (``ops.fe_null_skymax``
+on a HIP engine, :func:`_null_max_host` otherwise; docs/DESIGN.md
+section 13).
 """
 
 from __future__ import annotations
@@ -273,6 +281,185 @@ def _host_max_amplitudes(assemble, prods, coeffs):
     return femax, argmax, amps
 
 
+_NOT_PD = ("the product block [[ss, sc], [sc, cc]] of (pulsar {p}, draw {d}, "
+           "frequency {f}) is not positive definite: it is no covariance to "
+           "draw noise-only products from")
+
+
+def _null_factors(prods):
+    """Cholesky factors ``(l00, l10, l11)``, each (P, D, F), of the
+    per-pulsar blocks ``B_p = [[ss, sc], [sc, cc]]`` of ``prods``
+    (P, D, 5, F).  Raises ``ValueError`` naming the first (pulsar, draw,
+    frequency) whose block is not positive definite (``ss <= 0``, a Schur
+    complement ``<= 0`` or a non-finite value)."""
+    ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
+    with np.errstate(all="ignore"):
+        l00 = np.sqrt(ss)
+        l10 = sc / l00
+        schur = cc - l10 * l10
+        l11 = np.sqrt(schur)
+    ok = (np.isfinite(ss) & np.isfinite(cc) & np.isfinite(sc)
+          & np.isfinite(l10) & np.isfinite(schur) & (ss > 0) & (schur > 0))
+    if not ok.all():
+        p, d, f = (int(i) for i in np.argwhere(~ok)[0])
+        raise ValueError(_NOT_PD.format(p=p, d=d, f=f))
+    return l00, l10, l11
+
+
+def _null_draws(prods, z):
+    """Noise-only data products ``n = L z``: ``prods`` (P, D, 5, F) and
+    standard normals ``z`` (D, F, P, 2, R) -> ``(n_s, n_c)``, each
+    (P, D, F, R), distributed as ``(sr, cr)`` under noise alone."""
+    l00, l10, l11 = _null_factors(prods)
+    z0 = np.moveaxis(z[:, :, :, 0, :], 2, 0)  # (P, D, F, R)
+    z1 = np.moveaxis(z[:, :, :, 1, :], 2, 0)
+    return l00[..., None] * z0, l10[..., None] * z0 + l11[..., None] * z1
+
+
+def _null_max_host(prods, ant, z, rcond=1e-12):
+    """Host reference of ``ops.fe_null_skymax``: the sky maximum of Fe for
+    ``R`` noise-only realisations per (draw, frequency) column.
+
+    ``prods`` (P, D, 5, F) (planes ss, cc, sc are read), ``ant``
+    (nsky, P, 2), ``z`` (D, F, P, 2, R).  Returns ``(femax (R, D, F),
+    argmax (R, D, F) int64)``, the lowest sky index on ties.
+
+    Per sky point M is factored ONCE (the LDL^T and pivot rule of the
+    kernels, elementwise over the columns) and all R realisations go
+    through the forward solve; the columns whose M fails a pivot take the
+    pseudo-inverse, as in :func:`_assemble_fe_draws`.  Every step is
+    elementwise in R: a realisation's value does not depend on how many
+    others are computed with it."""
+    prods = np.asarray(prods, dtype=np.float64)
+    ant = np.asarray(ant, dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    P, D, _, F = prods.shape
+    if z.shape[:4] != (D, F, P, 2):
+        raise ValueError(f"z must be (D, F, P, 2, R) = ({D}, {F}, {P}, 2, R),"
+                         f" got {z.shape}")
+    R = z.shape[4]
+    ns, nc = _null_draws(prods, z)
+    ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
+    femax = np.full((D, F, R), -np.inf)
+    argmax = np.full((D, F, R), -1, dtype=np.int64)
+
+    def w(coeff, q):  # (P,) x (P, D, F[, R]) -> (D, F[, R])
+        return np.einsum("p,p...->...", coeff, q)
+
+    for k in range(ant.shape[0]):
+        fplus, fcross = ant[k, :, 0], ant[k, :, 1]
+        fp2, fx2, fpx = fplus**2, fcross**2, fplus * fcross
+        m00, m01, m11 = w(fp2, ss), w(fp2, sc), w(fp2, cc)
+        m02, m03, m13 = w(fpx, ss), w(fpx, sc), w(fpx, cc)
+        m22, m23, m33 = w(fx2, ss), w(fx2, sc), w(fx2, cc)
+        m12 = m03
+        N = [w(fplus, ns), w(fplus, nc), w(fcross, ns), w(fcross, nc)]
+
+        def pivot_ok(s, mjj):
+            return (s > rcond * mjj) & (s < np.inf)
+
+        with np.errstate(all="ignore"):
+            d0 = m00
+            ok = pivot_ok(d0, m00)
+            i0 = 1.0 / d0
+            l10, l20, l30 = m01 * i0, m02 * i0, m03 * i0
+            d1 = m11 - l10 * m01
+            ok &= pivot_ok(d1, m11)
+            i1 = 1.0 / d1
+            t21 = m12 - l20 * m01
+            t31 = m13 - l30 * m01
+            l21, l31 = t21 * i1, t31 * i1
+            d2 = m22 - l20 * m02 - l21 * t21
+            ok &= pivot_ok(d2, m22)
+            i2 = 1.0 / d2
+            t32 = m23 - l30 * m02 - l31 * t21
+            l32 = t32 * i2
+            d3 = m33 - l30 * m03 - l31 * t31 - l32 * t32
+            ok &= pivot_ok(d3, m33)
+            i3 = 1.0 / d3
+            e = [x[..., None] for x in
+                 (l10, l20, l30, l21, l31, l32, i0, i1, i2, i3)]
+            z0 = N[0]
+            z1 = N[1] - e[0] * z0
+            z2 = N[2] - e[1] * z0 - e[3] * z1
+            z3 = N[3] - e[2] * z0 - e[4] * z1 - e[5] * z2
+            fe = 0.5 * (z0 * z0 * e[6] + z1 * z1 * e[7] + z2 * z2 * e[8]
+                        + z3 * z3 * e[9])  # (D, F, R)
+        if not ok.all():
+            M = np.empty((D, F, 4, 4))
+            M[..., 0, 0] = m00
+            M[..., 0, 1] = M[..., 1, 0] = m01
+            M[..., 0, 2] = M[..., 2, 0] = m02
+            M[..., 0, 3] = M[..., 3, 0] = m03
+            M[..., 1, 1] = m11
+            M[..., 1, 2] = M[..., 2, 1] = m12
+            M[..., 1, 3] = M[..., 3, 1] = m13
+            M[..., 2, 2] = m22
+            M[..., 2, 3] = M[..., 3, 2] = m23
+            M[..., 3, 3] = m33
+            for d, f in np.argwhere(~ok):
+                Mi = np.linalg.pinv(M[d, f], rcond=rcond)
+                acc = 0.0
+                for i in range(4):
+                    xi = sum(Mi[i, j] * N[j][d, f] for j in range(4))
+                    acc = acc + N[i][d, f] * xi
+                fe[d, f] = 0.5 * acc
+        better = fe > femax  # strict: the first maximum stays
+        femax = np.where(better, fe, femax)
+        argmax = np.where(better, k, argmax)
+    return np.moveaxis(femax, 2, 0), np.moveaxis(argmax, 2, 0)
+
+
+def _null_chunks(prods, ant, nreal, seed, real_chunk, z, device, hip,
+                 gen=None):
+    """(nreal, D, F) null sky maxima of one product set, ``real_chunk``
+    realisations at a time.  ``prods`` / ``ant``: device tensors (``hip``)
+    or numpy arrays.  ``z`` (D, F, P, 2, nreal) bypasses the generator;
+    otherwise each chunk is ONE ``torch.randn`` call on ``device`` from
+    ``gen`` (a fresh generator seeded with ``seed`` when none is
+    passed)."""
+    P, D, F = prods.shape[0], prods.shape[1], prods.shape[3]
+    nreal, real_chunk = int(nreal), int(real_chunk)
+    if nreal < 1 or real_chunk < 1:
+        raise ValueError("nreal and real_chunk must be at least 1")
+    if z is not None:
+        if tuple(z.shape) != (D, F, P, 2, nreal):
+            raise ValueError(
+                f"z must be (D, F, P, 2, nreal) = ({D}, {F}, {P}, 2, "
+                f"{nreal}), got {tuple(z.shape)}")
+        z = torch.as_tensor(z, dtype=torch.float64)
+    elif gen is None:
+        gen = torch.Generator(device=device)
+        gen.manual_seed(int(seed))
+    out = np.empty((nreal, D, F))
+    for lo in range(0, nreal, real_chunk):
+        hi = min(lo + real_chunk, nreal)
+        if z is None:
+            zc = torch.randn((D, F, P, 2, hi - lo), generator=gen,
+                             dtype=torch.float64, device=device)
+        else:
+            zc = z[..., lo:hi]
+        if hip:
+            from fastfp_amd import ops
+
+            fm, _, _ = ops.fe_null_skymax(
+                prods, ant, zc.to(prods.device).contiguous())
+            out[lo:hi] = fm.cpu().numpy()
+        else:
+            out[lo:hi] = _null_max_host(prods, ant, zc.cpu().numpy())[0]
+    return out
+
+
+def false_alarm_probability(femax, null):
+    """False-alarm probability of observed maxima ``femax`` (...) against
+    null maxima ``null`` (nreal, ...), ``(1 + #{null >= femax}) / (1 +
+    nreal)`` along the first axis of ``null``: never zero, the observed
+    value counts as one draw of its own null."""
+    null = np.asarray(null)
+    return (1.0 + (null >= np.asarray(femax)[None]).sum(axis=0)) \
+        / (1.0 + null.shape[0])
+
+
 class FastFe:
     """Fe detection statistic over (frequency, sky).
 
@@ -453,6 +640,115 @@ class FastFe:
         prods = engine.sweep_products(sigmas=sigmas).cpu().numpy()
         fplus, fcross = gw_antenna_pattern(self.pos, *sky[0])
         return _assemble_fe(prods, fplus, fcross, amplitudes=True)
+
+    # ------------------------------------------------------------------
+    # significance of the sky maximum
+    # ------------------------------------------------------------------
+    def _null_inputs(self, freqs, sky, Nvecs, Ts, sigmas, device, engine):
+        """``(engine, prods (P, 1, 5, F), ant (nsky, P, 2))``: device
+        tensors from the HIP solve on a HIP engine, numpy arrays
+        otherwise."""
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        if engine is None:
+            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
+            engine.precompute(freqs)
+        if engine._use_hip:
+            prods = engine.sweep_products_hip(
+                _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
+            return (engine, prods[:, None].contiguous(),
+                    _antenna_table(self.pos, sky, engine.device))
+        prods = engine.sweep_products(sigmas=sigmas).cpu().numpy()
+        return engine, prods[:, None], _antenna_table(self.pos, sky)
+
+    def null_max(
+        self,
+        freqs,
+        sky,
+        Nvecs,
+        Ts,
+        sigmas,
+        nreal: int,
+        seed: int = 0,
+        device: str = None,
+        engine: FpEngine = None,
+        real_chunk: int = 256,
+        z=None,
+    ) -> np.ndarray:
+        """The sky-maximised Fe of ``nreal`` noise-only realisations per
+        frequency: ``(nreal, F)``, the Monte-Carlo null distribution of
+        what :meth:`sweep_max` returns.
+
+        No solve runs per realisation.  For residuals ``r ~ N(0, C)`` the
+        data products of pulsar ``p`` are exactly ``(sr, cr)_p ~ N(0,
+        [[ss, sc], [sc, cc]]_p)``, so a realisation is one standard-normal
+        pair per pulsar and frequency and a sky assembly in which only
+        the four ``N`` sums are new.  On a HIP engine the products come
+        from ``sweep_products_hip`` and ``ops.fe_null_skymax`` runs per
+        chunk of ``real_chunk`` realisations; on a CPU engine it is
+        :func:`_null_max_host`.
+
+        ``z`` is drawn on the engine's device by a ``torch.Generator``
+        seeded with ``seed``, one ``torch.randn`` call of shape (1, F, P,
+        2, chunk) per chunk: the stream, and so the result, is
+        reproducible for a given ``(seed, real_chunk, device type)`` and
+        is NOT the same on the CPU and on the GPU.  ``z=`` takes explicit
+        normals of shape (1, F, P, 2, nreal) and bypasses the generator
+        (the result then does not depend on ``real_chunk``).
+
+        Scope.  The null is exact per frequency.  Realisations are drawn
+        independently per frequency, so the joint distribution across
+        frequencies is not modelled and a trials factor over frequency is
+        out of scope; so is a signal-present mean for detection-
+        probability curves.
+        """
+        engine, prods, ant = self._null_inputs(freqs, sky, Nvecs, Ts, sigmas,
+                                               device, engine)
+        return _null_chunks(prods, ant, nreal, seed, real_chunk, z,
+                            engine.device, engine._use_hip)[:, 0, :]
+
+    def false_alarm(
+        self,
+        freqs,
+        sky,
+        Nvecs,
+        Ts,
+        sigmas,
+        nreal: int,
+        seed: int = 0,
+        device: str = None,
+        engine: FpEngine = None,
+        real_chunk: int = 256,
+        z=None,
+    ):
+        """The observed sky maximum and its false-alarm probability:
+        ``(femax (F,), argmax (F,), pfa (F,))`` with ``femax, argmax`` as
+        :meth:`sweep_max` returns them and
+
+            pfa = (1 + #{null >= femax}) / (1 + nreal)
+
+        per frequency against the ``nreal`` realisations of
+        :meth:`null_max` (same arguments, same stream, same scope: a
+        single-frequency probability, no trials factor over frequency).
+        The products and the antenna table are computed once and serve
+        both passes."""
+        engine, prods, ant = self._null_inputs(freqs, sky, Nvecs, Ts, sigmas,
+                                               device, engine)
+        if engine._use_hip:
+            from fastfp_amd import ops
+
+            fm, am, _ = ops.fe_skymax(prods, ant)
+            femax = fm[0].cpu().numpy()
+            argmax = am[0].cpu().numpy().astype(np.int64)
+        else:
+            # the assembly of ``sweep_max`` on a CPU engine, call for call
+            grid = np.stack([_assemble_fe(prods[:, 0], ant[k, :, 0],
+                                          ant[k, :, 1])
+                             for k in range(ant.shape[0])])
+            femax, argmax = np.nanmax(grid, axis=0), np.nanargmax(grid, axis=0)
+        null = _null_chunks(prods, ant, nreal, seed, real_chunk, z,
+                            engine.device, engine._use_hip)[:, 0, :]
+        return femax, argmax, false_alarm_probability(femax, null)
 
 
 def compute_Fe(psrs, pta, noise, freqs, sky, device=None) -> np.ndarray:
@@ -678,3 +974,56 @@ class NMFe:
         if amplitudes:
             return femax, argmax, amps
         return femax, argmax
+
+    def null_max(
+        self,
+        freqs,
+        sky,
+        samples: dict,
+        Nvecs,
+        Ts,
+        nreal: int,
+        seed: int = 0,
+        draw_chunk: int = 8,
+        real_chunk: int = 128,
+        engine: FpEngine = None,
+        compress: bool = False,
+        device: str = None,
+    ) -> np.ndarray:
+        """:meth:`FastFe.null_max` over noise draws: ``(nreal, D, F)``,
+        the sky-maximised Fe of ``nreal`` noise-only realisations for
+        every (draw, frequency), each draw's realisations drawn from that
+        draw's own products (``_products``; ``compress`` as in
+        :meth:`sweep`).
+
+        One generator seeded with ``seed`` serves all chunks, draw chunks
+        outermost: the stream is reproducible for a given ``(seed,
+        draw_chunk, real_chunk, device type)``.  On a HIP engine a chunk
+        holds the M factors of ``draw_chunk * F * nsky`` points (80 bytes
+        each) and ``draw_chunk * F * P * 2 * real_chunk`` normals, which
+        is what the two chunk sizes bound.  Scope as in
+        :meth:`FastFe.null_max`."""
+        from fastfp_amd.noise import batch_phiinv
+
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        engine = self._engine(engine, freqs, samples, Nvecs, Ts, device,
+                              compress)
+        phiinvs = batch_phiinv(self.rn_sigs, samples)
+        phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
+        D = phiinvs[0].shape[0]
+        F = engine.freqs.shape[0]
+        hip = engine._use_hip
+        ant = _antenna_table(self.fe.pos, sky, engine.device if hip else None)
+        gen = torch.Generator(device=engine.device)
+        gen.manual_seed(int(seed))
+        out = np.empty((int(nreal), D, F))
+        for lo in range(0, D, draw_chunk):
+            hi = min(lo + draw_chunk, D)
+            prods = self._products(engine, [p[lo:hi] for p in phiinvs],
+                                   compress, hip=hip)  # (P, Dc, 5, F)
+            if not hip:
+                prods = prods.cpu().numpy()
+            out[:, lo:hi] = _null_chunks(prods, ant, nreal, seed, real_chunk,
+                                         None, engine.device, hip, gen=gen)
+        return out

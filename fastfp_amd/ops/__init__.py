@@ -318,3 +318,79 @@ def fe_amplitudes(prods, ant, idx, repair: bool = True):
             amps[dk, fk] = torch.as_tensor(
                 a_h[:, 0], dtype=amps.dtype).to(amps.device)
     return amps, fe, status
+
+
+def fe_max_pulsars() -> int:
+    """Largest pulsar count of the Fe sky kernels (``fe_assemble``,
+    ``fe_skymax``, ``fe_null_skymax``)."""
+    return int(_fe_ext().fe_max_pulsars())
+
+
+def _null_lfac(prods):
+    """(D, F, P, 3) = [l00, l10, l11], the Cholesky factors of the
+    per-pulsar blocks [[ss, sc], [sc, cc]] of ``prods`` (P, D, 5, F), by
+    elementwise torch ops.  Raises ``ValueError`` naming the first
+    (pulsar, draw, frequency) whose block is not positive definite — one
+    ``.any()`` sync."""
+    ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
+    l00 = torch.sqrt(ss)
+    l10 = sc / l00
+    schur = cc - l10 * l10
+    l11 = torch.sqrt(schur)
+    ok = (torch.isfinite(ss) & torch.isfinite(cc) & torch.isfinite(sc)
+          & torch.isfinite(l10) & torch.isfinite(schur) & (ss > 0)
+          & (schur > 0))
+    if bool((~ok).any()):
+        from fastfp_amd.festat import _NOT_PD
+
+        p, d, f = torch.nonzero(~ok)[0].tolist()
+        raise ValueError(_NOT_PD.format(p=p, d=d, f=f))
+    return torch.stack([l00, l10, l11], dim=-1).permute(1, 2, 0, 3).contiguous()
+
+
+def fe_null_skymax(prods, ant, z, repair: bool = True, rtiles: int = 0):
+    """The sky maximum of Fe for ``R`` noise-only realisations per (draw,
+    frequency) column, on the device (docs/DESIGN.md section 13).
+
+    ``prods`` (P, D, 5, F) and ``ant`` (nsky, P, 2) as in
+    :func:`fe_skymax` (only the planes ss, cc, sc are read); ``z``
+    (D, F, P, 2, R) contiguous fp64 standard normals.  Realisation ``r``
+    of pulsar ``p`` has the data products ``n = L_p z_p[r]`` with ``L_p``
+    the Cholesky factor of ``[[ss, sc], [sc, cc]]_p``, which is how
+    ``(sr, cr)_p`` is distributed under noise alone.  A block that is not
+    positive definite raises ``ValueError`` naming its (pulsar, draw,
+    frequency).
+
+    Returns ``(femax (R, D, F) f64, argmax (R, D, F) int32, nskip (D, F)
+    int32)`` device tensors, the first two as permuted views of the
+    kernel's (D, F, R) output.  ``nskip`` counts the degenerate sky points
+    of a column (bitwise those of :func:`fe_skymax`: they do not depend
+    on the realisation).  With ``repair`` every column with ``nskip > 0``
+    is recomputed on the host over ALL sky points through
+    ``festat._null_max_host`` (pseudo-inverse at the degenerate points);
+    ``nskip`` keeps the kernel's counts.  ``rtiles``: realisation tiles
+    per workgroup (a tuning knob; no result depends on it).
+    """
+    ext = _fe_ext()
+    if prods.dim() != 4 or prods.shape[2] != 5:
+        raise RuntimeError("prods must be (P, D, 5, F)")
+    prods = prods.contiguous()
+    ant = ant.contiguous()
+    lfac = _null_lfac(prods)
+    femax, argmax, nskip = ext.fe_null_skymax(prods, ant, lfac, z, rtiles)
+    if repair:
+        bad = nskip > 0
+        if bool(bad.any()):
+            from fastfp_amd.festat import _null_max_host
+
+            d_idx, f_idx = torch.nonzero(bad, as_tuple=True)
+            # the bad columns as a (P, ncols, 5, 1) product set
+            sub = prods[:, d_idx, :, f_idx].permute(1, 0, 2).unsqueeze(-1)
+            zsub = z[d_idx, f_idx].unsqueeze(1)  # (ncols, 1, P, 2, R)
+            fm, am = _null_max_host(sub.cpu().numpy(), ant.cpu().numpy(),
+                                    zsub.cpu().numpy())  # (R, ncols, 1)
+            femax[d_idx, f_idx] = torch.as_tensor(
+                fm[:, :, 0].T.copy(), dtype=femax.dtype).to(femax.device)
+            argmax[d_idx, f_idx] = torch.as_tensor(
+                am[:, :, 0].T.copy(), dtype=argmax.dtype).to(argmax.device)
+    return femax.permute(2, 0, 1), argmax.permute(2, 0, 1), nskip

@@ -372,6 +372,71 @@ std::vector<torch::Tensor> fe_skymax(torch::Tensor prods, torch::Tensor ant) {
   return {femax, argmax, nskip};
 }
 
+// fe_mfactor: the LDL^T of every (column, sky) 4x4 M as the sky kernels
+// factor it -> fac (D, F, nsky, 10) = [l10, l20, l30, l21, l31, l32, 1/d0,
+// 1/d1, 1/d2, 1/d3]; ten NaNs at the points they skip.  Reads only the
+// planes ss, cc, sc of prods.
+torch::Tensor fe_mfactor(torch::Tensor prods, torch::Tensor ant) {
+  check_fe_inputs(prods, ant);
+  const int P = prods.size(0), D = prods.size(1), F = prods.size(3);
+  const int nsky = ant.size(0);
+  auto fac = torch::empty({D, F, nsky, fe_null_fac_numbers()},
+                          prods.options());
+  check_launch(
+      launch_fe_mfactor(prods.data_ptr<double>(), ant.data_ptr<double>(), P,
+                        D, F, nsky, fac.data_ptr<double>(), stream()),
+      "fe_mfactor");
+  return fac;
+}
+
+// fe_null_skymax: the sky maximum of R noise-only realisations per
+// column.  lfac (D,F,P,3) = Cholesky factors [l00, l10, l11] of the
+// per-pulsar blocks [[ss, sc], [sc, cc]], z (D,F,P,2,R) standard normals
+// -> femax (D,F,R) f64, argmax (D,F,R) i32 (lowest index on ties, -1 and
+// -inf if every point was skipped), nskip (D,F) i32.
+std::vector<torch::Tensor> fe_null_skymax(torch::Tensor prods,
+                                          torch::Tensor ant,
+                                          torch::Tensor lfac, torch::Tensor z,
+                                          int64_t rtiles) {
+  check_fe_shapes(prods, ant);
+  TORCH_CHECK(prods.size(0) >= 1 && prods.size(0) <= fe_max_pulsars(),
+              "the Fe null kernel keeps a (2, P, 16) realisation tile in LDS "
+              "next to the sky kernels' factor pass and supports 1 <= P <= ",
+              fe_max_pulsars(), " pulsars; got P=", prods.size(0));
+  check_fe_dims(prods, ant);
+  check_f64(lfac, "lfac");
+  check_f64(z, "z");
+  const int P = prods.size(0), D = prods.size(1), F = prods.size(3);
+  const int nsky = ant.size(0);
+  TORCH_CHECK(lfac.device() == prods.device() && z.device() == prods.device(),
+              "prods/lfac/z device mismatch");
+  TORCH_CHECK(lfac.dim() == 4 && lfac.size(0) == D && lfac.size(1) == F &&
+                  lfac.size(2) == P && lfac.size(3) == 3,
+              "lfac must be (D, F, P, 3) matching prods");
+  TORCH_CHECK(z.dim() == 5 && z.size(0) == D && z.size(1) == F &&
+                  z.size(2) == P && z.size(3) == 2,
+              "z must be (D, F, P, 2, R) matching prods");
+  TORCH_CHECK(z.size(4) < (1L << 31), "dimension overflow");
+  TORCH_CHECK(rtiles == 0 || rtiles == 1 || rtiles == 2 || rtiles == 4,
+              "rtiles must be 0 (default), 1, 2 or 4");
+  const int R = z.size(4);
+  auto iopts = prods.options().dtype(torch::kInt32);
+  auto femax = torch::full({D, F, R}, -INFINITY, prods.options());
+  auto argmax = torch::full({D, F, R}, -1, iopts);
+  auto nskip = torch::zeros({D, F}, iopts);
+  auto fac = torch::empty({D, F, nsky, fe_null_fac_numbers()},
+                          prods.options());
+  check_launch(
+      launch_fe_null_skymax(prods.data_ptr<double>(), ant.data_ptr<double>(),
+                            lfac.data_ptr<double>(), z.data_ptr<double>(), P,
+                            D, F, nsky, R, (int)rtiles,
+                            fac.data_ptr<double>(), femax.data_ptr<double>(),
+                            argmax.data_ptr<int>(), nskip.data_ptr<int>(),
+                            stream()),
+      "fe_null_skymax");
+  return {femax, argmax, nskip};
+}
+
 // diag_inv: invert the 16x16 diagonal blocks of batched lower-tri L
 // (B, mp, mp) -> invd (B, mp/16, 16, 16); the m > 128 direct path.
 torch::Tensor diag_inv(torch::Tensor L) {
@@ -451,4 +516,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Fe sky assembly fused with the maximum over sky points");
   m.def("fe_amplitudes", &fe_amplitudes,
         "Fe maximum-likelihood amplitudes at one sky index per column");
+  m.def("fe_mfactor", &fe_mfactor,
+        "LDL^T factors of the Fe 4x4 M per (column, sky) point");
+  m.def("fe_null_skymax", &fe_null_skymax,
+        "sky maximum of Fe over noise-only realisations n = L z",
+        py::arg("prods"), py::arg("ant"), py::arg("lfac"), py::arg("z"),
+        py::arg("rtiles") = 0);
+  m.def("fe_max_pulsars", &fe_max_pulsars,
+        "largest pulsar count of the Fe sky kernels");
 }

@@ -389,6 +389,381 @@ __global__ __launch_bounds__(FE_AMPS_THREADS) void fe_amps_kernel(
   status[n] = st;
 }
 
+// ---------------------------------------------------------------------
+// Null distribution of the sky maximum (docs/DESIGN.md section 13).
+//
+// Under noise alone (sr, cr)_p ~ N(0, [[ss, sc], [sc, cc]]_p), so one
+// realisation of a column (d, f) is n_p = L_p z_p with L_p the 2x2
+// Cholesky factor of that block (lfac) and z_p a standard-normal pair.
+// M does not depend on the realisation: fe_mfac_kernel factors it ONCE
+// per (column, sky) and fe_null_kernel only forms the four N sums,
+//   rows = sky, columns = realisations, K = P,
+// and pushes them through the stored factor.
+// ---------------------------------------------------------------------
+
+// the ten numbers of M = L D L^T that the forward solve reads
+enum {
+  FC_L10 = 0, FC_L20, FC_L30, FC_L21, FC_L31, FC_L32,
+  FC_I0, FC_I1, FC_I2, FC_I3,
+  FE_NFAC
+};
+
+// The LDL^T of fe_point, operation for operation, on the nine M sums
+// s[S_P2SS .. S_X2CC] (kept apart from fe_point so the sky kernels
+// compile exactly as before).  Returns false on the pivots fe_point
+// rejects.
+static __device__ __forceinline__ bool fe_point_factor(const double* s,
+                                                       double* fc) {
+  const double m00 = s[S_P2SS], m01 = s[S_P2SC], m02 = s[S_PXSS];
+  const double m03 = s[S_PXSC], m11 = s[S_P2CC], m12 = s[S_PXSC];
+  const double m13 = s[S_PXCC], m22 = s[S_X2SS], m23 = s[S_X2SC];
+  const double m33 = s[S_X2CC];
+
+  const double d0 = m00;
+  if (!fe_pivot_ok(d0, m00)) return false;
+  const double i0 = 1.0 / d0;
+  const double l10 = m01 * i0, l20 = m02 * i0, l30 = m03 * i0;
+
+  const double d1 = fma(-l10, m01, m11);
+  if (!fe_pivot_ok(d1, m11)) return false;
+  const double i1 = 1.0 / d1;
+  const double t21 = fma(-l20, m01, m12);
+  const double t31 = fma(-l30, m01, m13);
+  const double l21 = t21 * i1, l31 = t31 * i1;
+
+  const double d2 = fma(-l21, t21, fma(-l20, m02, m22));
+  if (!fe_pivot_ok(d2, m22)) return false;
+  const double i2 = 1.0 / d2;
+  const double t32 = fma(-l31, t21, fma(-l30, m02, m23));
+  const double l32 = t32 * i2;
+
+  const double d3 = fma(-l32, t32, fma(-l31, t31, fma(-l30, m03, m33)));
+  if (!fe_pivot_ok(d3, m33)) return false;
+  const double i3 = 1.0 / d3;
+
+  fc[FC_L10] = l10;
+  fc[FC_L20] = l20;
+  fc[FC_L30] = l30;
+  fc[FC_L21] = l21;
+  fc[FC_L31] = l31;
+  fc[FC_L32] = l32;
+  fc[FC_I0] = i0;
+  fc[FC_I1] = i1;
+  fc[FC_I2] = i2;
+  fc[FC_I3] = i3;
+  return true;
+}
+
+// The M factors of every (column, sky) point: the blocking, staging and
+// K loop of fe_sky_kernel with the nine M sums only (same a and b
+// values, same k order: the sums are bitwise those of fe_skymax), then
+// fe_point_factor per lane.
+// grid = ceil(D*F / 16);  block = 256;  dynamic LDS = 3 * Kp * 16 doubles
+// fac (D*F, nsky, FE_NFAC); a skipped point is ten NaNs (FC_I0 is the
+// flag fe_null_kernel tests).
+__global__ __launch_bounds__(FE_THREADS, 4) void fe_mfac_kernel(
+    const double* __restrict__ prods /*(P, D, 5, F)*/,
+    const double* __restrict__ ant /*(nsky, P, 2)*/, int P, int D, int F,
+    int nsky, double* __restrict__ fac /*(D*F, nsky, FE_NFAC)*/) {
+  extern __shared__ double Bs[];  // [3][Kp][16]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+  const int li = lane & 15;
+  const int lk = lane >> 4;
+  const int Kp = (P + 3) & ~3;
+  const int nks = Kp >> 2;
+  const long NC = (long)D * F;
+  const long n0 = (long)blockIdx.x * 16;
+
+  {
+    const int j = tid & 15;
+    const long n = n0 + j;
+    const bool cok = n < NC;
+    const long d = cok ? n / F : 0;
+    const long f = cok ? n % F : 0;
+    const long cbase = d * 5 * F + f;
+    for (int r = tid >> 4; r < 3 * Kp; r += FE_THREADS / 16) {
+      const int k = r / 3;
+      const int c = r - 3 * k;
+      double v = 0.0;
+      if (cok && k < P) v = prods[(long)k * D * 5 * F + cbase + (long)c * F];
+      Bs[((long)c * Kp + k) * 16 + j] = v;
+    }
+  }
+  __syncthreads();
+
+  const long ncol = n0 + li;
+  const bool colok = ncol < NC;
+
+  const int nst = (nsky + 15) >> 4;
+  for (int st = wv; st < nst; st += FE_WAVES) {
+    const int s0 = st << 4;
+    const int arow = s0 + li;
+    const bool aok = arow < nsky;
+    const double* ap = ant + (long)(aok ? arow : 0) * P * 2;
+
+    f64x4 acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = f64x4{0, 0, 0, 0};
+
+    double fp = 0.0, fx = 0.0;
+    if (aok && lk < P) {
+      fp = ap[2 * lk];
+      fx = ap[2 * lk + 1];
+    }
+    for (int ks = 0; ks < nks; ++ks) {
+      const int k = 4 * ks + lk;
+      double nfp = 0.0, nfx = 0.0;
+      if (aok && k + 4 < P) {
+        nfp = ap[2 * (k + 4)];
+        nfx = ap[2 * (k + 4) + 1];
+      }
+      const double p2 = fp * fp, px = fp * fx, x2 = fx * fx;
+      const double bss = Bs[((long)0 * Kp + k) * 16 + li];
+      const double bcc = Bs[((long)1 * Kp + k) * 16 + li];
+      const double bsc = Bs[((long)2 * Kp + k) * 16 + li];
+      acc[S_P2SS] = MFMA_F64(p2, bss, acc[S_P2SS]);
+      acc[S_P2SC] = MFMA_F64(p2, bsc, acc[S_P2SC]);
+      acc[S_P2CC] = MFMA_F64(p2, bcc, acc[S_P2CC]);
+      acc[S_PXSS] = MFMA_F64(px, bss, acc[S_PXSS]);
+      acc[S_PXSC] = MFMA_F64(px, bsc, acc[S_PXSC]);
+      acc[S_PXCC] = MFMA_F64(px, bcc, acc[S_PXCC]);
+      acc[S_X2SS] = MFMA_F64(x2, bss, acc[S_X2SS]);
+      acc[S_X2SC] = MFMA_F64(x2, bsc, acc[S_X2SC]);
+      acc[S_X2CC] = MFMA_F64(x2, bcc, acc[S_X2CC]);
+      fp = nfp;
+      fx = nfx;
+    }
+
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int sky = s0 + 4 * v + lk;
+      if (!colok || sky >= nsky) continue;
+      double s[9], fc[FE_NFAC];
+#pragma unroll
+      for (int i = 0; i < 9; ++i) s[i] = acc[i][v];
+      const bool ok = fe_point_factor(s, fc);
+      double* out = fac + (ncol * nsky + sky) * FE_NFAC;
+#pragma unroll
+      for (int i = 0; i < FE_NFAC; ++i) out[i] = ok ? fc[i] : NAN;
+    }
+  }
+}
+
+// Null sky maximum.  One workgroup (4 waves) owns ONE column (d, f) and
+// RT tiles of 16 realisations; grid = D*F * ngrp, ngrp = ceil(R / 16 RT),
+// the groups of a column adjacent so they share its factors in L2.
+// The realisations n = L z are formed while staging (z is contiguous in
+// R: a wave reads consecutive doubles) into Ns[2][RT][Kp][16], the
+// conflict-free b layout of fe_sky_kernel per tile.  Wave w walks sky
+// tiles w, w+4, ...: ONE a load feeds 4 RT MFMAs per k-step, and the ten
+// factor numbers of a lane's four sky rows are read once per sky tile
+// for all RT tiles.  The forward solve is fe_point's on the stored
+// factor.  A realisation is one b column and one accumulator column: its
+// result does not depend on RT, on its tile or on its block.
+// dynamic LDS = 2 * RT * Kp * 16 doubles
+template <int RT>
+__global__ __launch_bounds__(FE_THREADS, RT == 4 ? 2 : 4) void fe_null_kernel(
+    const double* __restrict__ ant /*(nsky, P, 2)*/,
+    const double* __restrict__ lfac /*(D*F, P, 3)*/,
+    const double* __restrict__ z /*(D*F, P, 2, R)*/,
+    const double* __restrict__ fac /*(D*F, nsky, FE_NFAC)*/, int P, int nsky,
+    int R, int ngrp, double* __restrict__ femax /*(D*F, R)*/,
+    int* __restrict__ argmax /*(D*F, R)*/, int* __restrict__ nskip /*(D*F)*/) {
+  extern __shared__ double Ns[];  // [2][RT][Kp][16]
+  __shared__ double red_v[FE_WAVES][16 * RT];
+  __shared__ int red_i[FE_WAVES][16 * RT];
+  __shared__ int red_n[FE_WAVES];
+
+  constexpr int W = 16 * RT;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+  const int li = lane & 15;  // a row (sky) / b,acc column (realisation)
+  const int lk = lane >> 4;  // k index / acc row group
+  const int Kp = (P + 3) & ~3;
+  const int nks = Kp >> 2;
+  const long col = blockIdx.x / ngrp;
+  const int grp = blockIdx.x - (int)(col * ngrp);
+  const long r0 = (long)grp * W;
+
+  // stage n_s = l00 z0, n_c = l10 z0 + l11 z1; zero for k >= P, r >= R
+  for (int e = tid; e < Kp * W; e += FE_THREADS) {
+    const int k = e / W;
+    const int j = e - k * W;
+    const long r = r0 + j;
+    double ns = 0.0, nc = 0.0;
+    if (k < P && r < R) {
+      const double* lp = lfac + (col * P + k) * 3;
+      const double* zp = z + (col * P + k) * 2 * R + r;
+      const double z0 = zp[0], z1 = zp[R];
+      ns = lp[0] * z0;
+      nc = fma(lp[1], z0, lp[2] * z1);
+    }
+    const long o = ((long)(j >> 4) * Kp + k) * 16 + (j & 15);
+    Ns[o] = ns;
+    Ns[(long)RT * Kp * 16 + o] = nc;
+  }
+  __syncthreads();
+
+  double best[RT];
+  int besti[RT];
+#pragma unroll
+  for (int t = 0; t < RT; ++t) {
+    best[t] = -INFINITY;
+    besti[t] = -1;
+  }
+  int nsk = 0;
+  const double* fcol = fac + col * nsky * FE_NFAC;
+
+  const int nst = (nsky + 15) >> 4;
+  for (int st = wv; st < nst; st += FE_WAVES) {
+    const int s0 = st << 4;
+    const int arow = s0 + li;
+    const bool aok = arow < nsky;
+    const double* ap = ant + (long)(aok ? arow : 0) * P * 2;
+
+    f64x4 acc[4 * RT];
+#pragma unroll
+    for (int i = 0; i < 4 * RT; ++i) acc[i] = f64x4{0, 0, 0, 0};
+
+    double fp = 0.0, fx = 0.0;
+    if (aok && lk < P) {
+      fp = ap[2 * lk];
+      fx = ap[2 * lk + 1];
+    }
+    for (int ks = 0; ks < nks; ++ks) {
+      const int k = 4 * ks + lk;
+      double nfp = 0.0, nfx = 0.0;
+      if (aok && k + 4 < P) {
+        nfp = ap[2 * (k + 4)];
+        nfx = ap[2 * (k + 4) + 1];
+      }
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        const double bs = Ns[((long)t * Kp + k) * 16 + li];
+        const double bc = Ns[((long)(RT + t) * Kp + k) * 16 + li];
+        acc[4 * t + 0] = MFMA_F64(fp, bs, acc[4 * t + 0]);
+        acc[4 * t + 1] = MFMA_F64(fp, bc, acc[4 * t + 1]);
+        acc[4 * t + 2] = MFMA_F64(fx, bs, acc[4 * t + 2]);
+        acc[4 * t + 3] = MFMA_F64(fx, bc, acc[4 * t + 3]);
+      }
+      fp = nfp;
+      fx = nfx;
+    }
+
+    // per-lane epilogue: sky rows 4v + lk, realisations t * 16 + li
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int sky = s0 + 4 * v + lk;
+      if (sky >= nsky) continue;
+      const double* fc = fcol + (long)sky * FE_NFAC;
+      const double i0 = fc[FC_I0];
+      if (!(i0 == i0)) {  // skipped by the pivot rule
+        ++nsk;
+        continue;
+      }
+      const double l10 = fc[FC_L10], l20 = fc[FC_L20], l30 = fc[FC_L30];
+      const double l21 = fc[FC_L21], l31 = fc[FC_L31], l32 = fc[FC_L32];
+      const double i1 = fc[FC_I1], i2 = fc[FC_I2], i3 = fc[FC_I3];
+#pragma unroll
+      for (int t = 0; t < RT; ++t) {
+        const double z0 = acc[4 * t + 0][v];
+        const double z1 = fma(-l10, z0, acc[4 * t + 1][v]);
+        const double z2 = fma(-l21, z1, fma(-l20, z0, acc[4 * t + 2][v]));
+        const double z3 =
+            fma(-l32, z2, fma(-l31, z1, fma(-l30, z0, acc[4 * t + 3][v])));
+        const double val =
+            0.5 * fma(z3 * z3, i3, fma(z2 * z2, i2, fma(z1 * z1, i1, z0 * z0 * i0)));
+        // sky ascends per lane: the first maximum stays; a non-finite
+        // value (non-finite z) never becomes the maximum
+        if ((fabs(val) < INFINITY) && val > best[t]) {
+          best[t] = val;
+          besti[t] = sky;
+        }
+      }
+    }
+  }
+
+  // row groups lk = 0..3 share the realisation: lanes +16, +32
+#pragma unroll
+  for (int off = 16; off <= 32; off <<= 1) {
+    nsk += __shfl_xor(nsk, off, 64);
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      const double ov = __shfl_xor(best[t], off, 64);
+      const int oi = __shfl_xor(besti[t], off, 64);
+      if (ov > best[t] ||
+          (ov == best[t] && oi >= 0 && (besti[t] < 0 || oi < besti[t]))) {
+        best[t] = ov;
+        besti[t] = oi;
+      }
+    }
+  }
+  if (lk == 0) {
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      red_v[wv][t * 16 + li] = best[t];
+      red_i[wv][t * 16 + li] = besti[t];
+    }
+    if (li == 0) red_n[wv] = nsk;  // the same count in every column
+  }
+  __syncthreads();
+  if (wv == 0 && lk == 0) {
+#pragma unroll
+    for (int t = 0; t < RT; ++t) {
+      double b = best[t];
+      int bi = besti[t];
+#pragma unroll
+      for (int w = 1; w < FE_WAVES; ++w) {
+        const double ov = red_v[w][t * 16 + li];
+        const int oi = red_i[w][t * 16 + li];
+        if (ov > b || (ov == b && oi >= 0 && (bi < 0 || oi < bi))) {
+          b = ov;
+          bi = oi;
+        }
+      }
+      const long r = r0 + t * 16 + li;
+      if (r < R) {
+        femax[col * R + r] = b;
+        argmax[col * R + r] = bi;
+      }
+    }
+    if (grp == 0 && li == 0)
+      nskip[col] = red_n[0] + red_n[1] + red_n[2] + red_n[3];
+  }
+}
+
+// Realisation tiles per workgroup of fe_null_kernel when the caller asks
+// for none (rtiles = 0): measured in docs/DESIGN.md section 13.
+#define FE_NULL_RT 2
+// dynamic LDS a workgroup may ask for next to the static reduction slots
+#define FE_NULL_LDS_MAX (144 * 1024)
+
+template <int RT>
+static hipError_t fe_null_launch(const double* ant, const double* lfac,
+                                 const double* z, const double* fac, int P,
+                                 long NC, int nsky, int R, double* femax,
+                                 int* argmax, int* nskip,
+                                 hipStream_t stream) {
+  const int Kp = (P + 3) & ~3;
+  const size_t lds = (size_t)2 * RT * Kp * 16 * sizeof(double);
+  const long ngrp = ((long)R + 16 * RT - 1) / (16 * RT);
+  if (NC * ngrp > 0x7fffffffL) return hipErrorInvalidValue;
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(
+        (const void*)fe_null_kernel<RT>,
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(fe_null_kernel<RT>, dim3((unsigned)(NC * ngrp)),
+                     dim3(FE_THREADS), lds, stream, ant, lfac, z, fac, P,
+                     nsky, R, (int)ngrp, femax, argmax, nskip);
+  return hipGetLastError();
+}
+
 extern "C" {
 
 // Largest P the resident product tile supports: 5 * Kp * 16 doubles of
@@ -446,6 +821,56 @@ int launch_fe_amplitudes(const double* prods, const double* ant,
                      dim3(FE_AMPS_THREADS), 0, stream, prods, ant, idx, P, D,
                      F, nsky, amps, fe, status);
   return (int)hipGetLastError();
+}
+
+int fe_null_fac_numbers() { return FE_NFAC; }
+
+int launch_fe_mfactor(const double* prods, const double* ant, int P, int D,
+                      int F, int nsky, double* fac, hipStream_t stream) {
+  const int Kp = (P + 3) & ~3;
+  const size_t lds = (size_t)3 * Kp * 16 * sizeof(double);
+  const long ntiles = ((long)D * F + 15) / 16;
+  if (ntiles == 0 || nsky == 0) return (int)hipSuccess;
+  if (ntiles > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  if (lds > 48 * 1024) {
+    hipError_t e = hipFuncSetAttribute(
+        (const void*)fe_mfac_kernel,
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(fe_mfac_kernel, dim3((unsigned)ntiles), dim3(FE_THREADS),
+                     lds, stream, prods, ant, P, D, F, nsky, fac);
+  return (int)hipGetLastError();
+}
+
+int launch_fe_null_skymax(const double* prods, const double* ant,
+                          const double* lfac, const double* z, int P, int D,
+                          int F, int nsky, int R, int rtiles, double* fac,
+                          double* femax, int* argmax, int* nskip,
+                          hipStream_t stream) {
+  const long NC = (long)D * F;
+  if (NC == 0 || nsky == 0 || R == 0) return (int)hipSuccess;
+  if (rtiles != 0 && rtiles != 1 && rtiles != 2 && rtiles != 4)
+    return (int)hipErrorInvalidValue;
+  int e = launch_fe_mfactor(prods, ant, P, D, F, nsky, fac, stream);
+  if (e != 0) return e;
+  // no more tiles than R fills, no more than the LDS holds at this P
+  int rt = rtiles ? rtiles : FE_NULL_RT;
+  const int Kp = (P + 3) & ~3;
+  while (rt > 1 && (R <= 8 * rt ||
+                    (size_t)2 * rt * Kp * 16 * sizeof(double) > FE_NULL_LDS_MAX))
+    rt >>= 1;
+  hipError_t err;
+  if (rt == 4)
+    err = fe_null_launch<4>(ant, lfac, z, fac, P, NC, nsky, R, femax, argmax,
+                            nskip, stream);
+  else if (rt == 2)
+    err = fe_null_launch<2>(ant, lfac, z, fac, P, NC, nsky, R, femax, argmax,
+                            nskip, stream);
+  else
+    err = fe_null_launch<1>(ant, lfac, z, fac, P, NC, nsky, R, femax, argmax,
+                            nskip, stream);
+  return (int)err;
 }
 
 }  // extern "C"

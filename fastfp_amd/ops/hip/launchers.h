@@ -89,4 +89,26 @@ int launch_fe_amplitudes(const double* prods, const double* ant,
                          double* amps, double* fe, int* status,
                          hipStream_t stream);
 
+// numbers per (column, sky) point of the stored M factor
+int fe_null_fac_numbers();
+
+// prods (P,D,5,F) planes ss, cc, sc and ant (nsky,P,2) -> fac
+// (D*F, nsky, fe_null_fac_numbers()): the LDL^T of every 4x4 M as the
+// sky kernels factor it, NaN where they skip the point
+int launch_fe_mfactor(const double* prods, const double* ant, int P, int D,
+                      int F, int nsky, double* fac, hipStream_t stream);
+
+// Null sky maximum: launch_fe_mfactor into the caller's scratch `fac`,
+// then per realisation r the maximum over sky of Fe with N built from
+// n = lfac z.  lfac (D,F,P,3) = [l00, l10, l11], z (D,F,P,2,R) -> femax,
+// argmax (D,F,R), nskip (D,F); the caller initialises the three outputs.
+// rtiles = realisation tiles per workgroup (1, 2 or 4; 0 = the default);
+// the launcher lowers it to what R fills and the LDS holds, and no
+// result depends on it.
+int launch_fe_null_skymax(const double* prods, const double* ant,
+                          const double* lfac, const double* z, int P, int D,
+                          int F, int nsky, int R, int rtiles, double* fac,
+                          double* femax, int* argmax, int* nskip,
+                          hipStream_t stream);
+
 }  // extern "C"

@@ -22,7 +22,11 @@ fe_amplitudes at the argmax);
 defaults P=67, D=256, F=200, nsky=768, m=120.  It also times the
 products solve at the compressed shape (m / 2 variable columns padded in
 front to mp, gsign = -1): trsm_prods and trsm_prods_store on the same
-padded system.
+padded system.  Last it times the null sky maximum (fe_null_skymax, D = 1,
+R = 1024 realisations, with 1, 2 and 4 realisation tiles per workgroup,
+and its factor pass fe_mfactor alone) in rounds alternated with the route
+that needs no new kernel: fe_skymax on products replicated to (P, R, 5, F)
+with the realisations in the planes sr, cr.
 """
 
 import sys
@@ -298,6 +302,65 @@ def main_fe(P=67, D=256, F=200, nsky=768, m=120):
     assert int(status.sum()) == 0, "bench inputs must be non-degenerate"
     rel = float(((fe_a - femax).abs() / femax).max())
     print(f"check: status=0, fe at argmax vs femax max rel diff {rel:.2e}")
+    del prods, fmap, femax, argmax, nskip, amps, fe_a, status
+    main_fe_null(P, F, nsky, ant, rng)
+
+
+def main_fe_null(P, F, nsky, ant, rng, R=1024, rounds=5):
+    """Null sky maximum at D = 1: the new kernel against fe_skymax on
+    replicated products (what the parent of the kernel offers).  Only the
+    fe_skymax call of that route is timed: building its (P, R, 5, F)
+    input is left out, in its favour."""
+    prods = np.empty((P, 1, 5, F))
+    prods[:, :, 0:2] = rng.uniform(1.0, 2.0, (P, 1, 2, F))
+    prods[:, :, 2] = 0.1 * rng.normal(size=(P, 1, F))
+    prods[:, :, 3:] = 0.0
+    prods = torch.as_tensor(prods, device=DEV)
+    z = torch.as_tensor(rng.standard_normal((1, F, P, 2, R)), device=DEV)
+    ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]  # (P, 1, F)
+    l00 = torch.sqrt(ss)
+    l10 = sc / l00
+    l11 = torch.sqrt(cc - l10 * l10)
+    lfac = torch.stack([l00, l10, l11], dim=-1).permute(1, 2, 0, 3).contiguous()
+    # the replicated route's input: draw r = realisation r
+    zt = z[0].permute(1, 2, 3, 0)  # (P, 2, R, F)
+    rep = prods.expand(P, R, 5, F).clone()
+    rep[:, :, 3] = l00 * zt[:, 0]
+    rep[:, :, 4] = l10 * zt[:, 0] + l11 * zt[:, 1]
+    wmax, warg, wskip = ext.fe_skymax(rep, ant)
+    femax, argmax, nskip = ext.fe_null_skymax(prods, ant, lfac, z)
+    assert int(wskip.sum()) == 0 and int(nskip.sum()) == 0
+    got = femax[0].t()  # (R, F)
+    rel = float(((got - wmax).abs() / wmax).max())
+    same = float((argmax[0].t() == warg).double().mean())
+    print(f"check: fe_null_skymax vs replicated fe_skymax max rel diff "
+          f"{rel:.2e}, argmax equal at {same:.6f} of the points")
+    assert rel < 1e-9
+    arms = {
+        "fe_skymax replicated": lambda: ext.fe_skymax(rep, ant),
+        "fe_null_skymax rtiles=1": lambda: ext.fe_null_skymax(
+            prods, ant, lfac, z, 1),
+        "fe_null_skymax rtiles=2": lambda: ext.fe_null_skymax(
+            prods, ant, lfac, z, 2),
+        "fe_null_skymax rtiles=4": lambda: ext.fe_null_skymax(
+            prods, ant, lfac, z, 4),
+        "fe_null_skymax default": lambda: ext.fe_null_skymax(
+            prods, ant, lfac, z),
+        "fe_mfactor alone": lambda: ext.fe_mfactor(prods, ant),
+    }
+    ts = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            ts[k].append(timeit(fn, iters=20, warmup=3))
+    points = float(nsky) * R * F
+    for k, v in ts.items():
+        t = float(np.median(v))
+        nsum = 13 if "replicated" in k else 4
+        tf = "" if "mfactor" in k else \
+            f"  {points * nsum * 2 * P / t / 1e12:6.2f} TF/s ({nsum} sums)"
+        print(f"{k:26s} P={P} F={F} nsky={nsky} R={R}: {t*1e3:9.3f} ms{tf}"
+              f"  ({rounds} rounds: min {min(v)*1e3:.3f}, "
+              f"max {max(v)*1e3:.3f})")
 
 
 if __name__ == "__main__":
