@@ -76,6 +76,9 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 #define MFMA_F64(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 0)
+// c - a (x) b: for f64 the last operand is the NEG field, bit 0 negates A
+// (printed neg:[1,0,0]); -a*b is exact, so this is MFMA_F64(-a, b, c)
+#define MFMA_F64_NEGA(a, b, c) __builtin_amdgcn_mfma_f64_16x16x4f64((a), (b), (c), 0, 0, 1)
 
 static __device__ __forceinline__ double wave_reduce_sum(double v) {
   // fixed-order binary tree over the 64-lane wave
@@ -749,19 +752,22 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
 // (pulsar, frequency tile, draw slice [dlo, dhi)): its RHS strip (in
 // registers) and its sNs/sNr entries (in LDS) are loaded ONCE and every
 // draw of the slice is solved from them, so the per-draw traffic is the
-// factor alone.  Draw d+1's factor is fetched into registers before
-// draw d's MFMAs and written to the other LDS buffer after them: one
-// barrier per draw.  fp[p, d, f] is a plain store and is never read.
-// NBT 1..4 (mp <= 64).
+// factor alone.  Draw d+1's factor goes from L and invd straight into
+// the other LDS buffer by 16-byte direct loads (global_load_lds_dwordx4,
+// no register in between) issued in front of draw d's MFMAs and waited
+// for at draw d's barrier: one barrier per draw.  fp[p, d, f] is a plain
+// store and is never read.  NBT 1..4 (mp <= 64).
 //
 // Same numbers as trsm_fp_kernel accumulating into zeros, bit for bit:
 // the MFMA order per column, the acc/acc2 split, the order of every fma
 // chain of the lane-split reduction and fp_close are its own.  Three
 // things differ in form only:
-//   * the strict-lower panels are staged NEGATED and acc starts at +RHS,
-//     so acc holds the exact negative of trsm_fp_kernel's (every fma of
-//     the chain is sign-symmetric) and the diagonal solve takes it as it
-//     is — no negation of 8 + 8 registers per row block per draw;
+//   * the strict-lower panels sit in LDS as the factor kernel wrote them
+//     and their MFMAs negate the a operand (neg:[1,0,0], free and exact),
+//     with acc starting at +RHS: acc holds the exact negative of
+//     trsm_fp_kernel's (every fma of the chain is sign-symmetric) and the
+//     diagonal solve takes it as it is — no negation of 8 + 8 registers
+//     per row block per draw, and none of the staged panels either;
 //   * the w*w and w*partner sums of row block rb are taken as soon as
 //     W[rb] exists, in the shadow of the next row block's MFMAs; only
 //     the w*u sum waits for the barrier that publishes the u column;
@@ -788,28 +794,29 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_kernel(
 // LDS (one array, 48.5 KiB at NBT=4):
 //   2 buffers x (NBT(NBT-1)/2 strict-lower + NBT inverted-diagonal)
 //     16x16 blocks, rows padded to 18 doubles: the a-fragment read
-//     18*li + lk is conflict-free over a 32-lane half;
+//     18*li + lk is conflict-free over a 32-lane half.  A buffer is
+//     (NLB + NBT) * 144 16-byte pieces in lane-linear order, nine per
+//     row, which is what a direct load writes (wave base + lane * 16);
+//     the ninth piece of a row, the pad, is a second copy of the eighth;
 //   2 x mp doubles: the solved u column, by draw parity;
 //   5 x 64 doubles: sNs/sNr of the tile's frequencies.
 // block = 512 (8 waves), tile = 63 frequencies + u as in trsm_fp_kernel.
 // Registers as compiled (gfx950, -O3), SKIP = 0 / 1 / 2 / 3: NBT=4
-// 128 / 127 / 125 / 123 VGPR, 4 waves/SIMD (two workgroups per CU;
-// SKIP = 0 has 8 bytes of spill, reloaded once per draw, the others
-// none); NBT=3 104 / 95 / 100 / 98, NBT=2 72 / 71 / 69 / 67, NBT=1
-// 46 / 44 / 42 / 40.  RHS copy 8*NBT, W 8*NBT, the three accumulators
-// 24, the prefetched factor 4*NBT.  LDS is the same for every SKIP.
+// 106 / 104 / 98 / 96 VGPR, 4 waves/SIMD (two workgroups per CU), NBT=3
+// 79 / 77 / 82 / 72, NBT=2 61 / 59 / 57 / 55, NBT=1 42 / 40 / 38 / 36;
+// no scratch anywhere.  RHS copy 8*NBT, W 8*NBT, the three accumulators
+// 24, the source pointers and strides of the direct loads
+// 3 * ceil((NLB + NBT) * 144 / 512).  LDS is the same for every SKIP.
 //
 // PRODS: products mode (Fe), as trsm_fp_kernel's — the closing lane
 // stores the five corrected products into out[((p*D + d)*5 + i)*F + f]
 // (plain vector stores, every entry written, none read) instead of
 // closing them to Fp.  Solve, staging and the three sums are shared, so
 // the values equal trsm_fp_kernel<NBT, 1, true>'s bit for bit at every
-// SKIP.  As compiled, all 16 PRODS instantiations have the VGPR count,
-// spill (8 bytes at NBT=4 SKIP=0 only) and LDS of the Fp instantiation
-// with the same NBT and SKIP in the table above; SGPRs are 44 / 50 / 52 /
-// 54 at NBT 1..4 (43 at NBT=1 SKIP=3) against 44 / 50 / 50 / 50 (43).
-// The PRODS = false instantiations compile to the same instructions as
-// before the mode existed.
+// SKIP.  As compiled, all 16 PRODS instantiations have the VGPR and
+// SGPR counts and the LDS of the Fp instantiation with the same NBT and
+// SKIP in the table above (SGPRs 42 / 44 / 42 / 42 at NBT 1..4, 40 at
+// NBT=1 SKIP=3).
 // ---------------------------------------------------------------------
 #define DL_BS 18              // row stride of a staged block (doubles)
 #define DL_BLK (16 * DL_BS)   // doubles per staged block
@@ -839,9 +846,6 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
   constexpr int UC = 126;  // block column of u
   constexpr int NLB = NBT * (NBT - 1) / 2;  // strict-lower blocks
   constexpr int BUF = (NLB + NBT) * DL_BLK;
-  // 16-byte pieces: rb*128 per row panel, NBT*128 of inverted diagonals,
-  // at most one per thread each
-  static_assert(NBT * 128 <= 512, "one prefetch slot per panel");
   __shared__ __attribute__((aligned(16))) double S[2 * BUF + 2 * mp + 5 * 64];
 
   const int ntile = (F + DL_FREQS - 1) / DL_FREQS;
@@ -867,44 +871,49 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
   const int li = lane & 15;    // a-frag row / strip column
   const int lk = lane >> 4;    // k index / acc row group
 
-  // factor of draw d -> registers, 16 bytes per thread and panel: the
-  // inverted diagonal blocks, then the strict-lower row panels.  Every
-  // thread loads — past the end of a panel it re-reads the panel's last
-  // piece, which stage() drops — so no load sits behind a branch.
-  // (f64x2, not HIP's double2: an array of that struct is not promoted
-  // to registers.)
-  f64x2 pre[NBT];  // [0]: inverted diagonals, [rb]: row panel rb
-  auto fetch = [&](int d) {
-    const double* Ld = L + (long)d * mp * mp;
-    pre[0] = reinterpret_cast<const f64x2*>(
-        invd + (long)d * NBT * 256)[min(tid, NBT * 128 - 1)];
+  // factor of the next draw -> LDS buffer `buf` by 16-byte direct loads
+  // (no register in between).  The staged image is NP 16-byte pieces,
+  // nine per 18-double row; piece p of it comes from block p / 144, row
+  // (p % 144) / 9, and the ninth piece of a row — the two pad doubles no
+  // a-fragment reads — re-reads the row's eighth, so every source is
+  // inside L or invd.  A thread owns pieces tid + 512 i: their sources
+  // are found once per slice and advance by one draw per call.  The
+  // destination of a wave's load is its base + lane * 16, which is the
+  // image's own order.
+  constexpr int NP = (NLB + NBT) * (DL_BLK / 2);
+  constexpr int NPT = (NP + 511) / 512;  // pieces per thread
+  const double* src[NPT];
+  int inc[NPT];  // doubles from one draw's piece to the next draw's
 #pragma unroll
-    for (int rb = 1; rb < NBT; ++rb) {
-      const int idx = min(tid, rb * 128 - 1);
-      const int r = idx / (rb * 8), c = 2 * (idx % (rb * 8));
-      pre[rb] =
-          *reinterpret_cast<const f64x2*>(Ld + (rb * 16 + r) * mp + c);
+  for (int i = 0; i < NPT; ++i) {
+    const int p = min(tid + 512 * i, NP - 1);
+    const int blk = p / (DL_BLK / 2), r = (p % (DL_BLK / 2)) / 9;
+    const int c = 2 * min(p % 9, 7);
+    if (blk < NLB) {  // strict-lower block rb(rb-1)/2 + cb of L
+      const int rb = 1 + (blk >= 1) + (blk >= 3);
+      const int cb = blk - rb * (rb - 1) / 2;
+      src[i] = L + (long)dlo * mp * mp + (rb * 16 + r) * mp + cb * 16 + c;
+      inc[i] = mp * mp;
+    } else {  // inverted diagonal block blk - NLB
+      src[i] = invd + (long)dlo * NBT * 256 + (blk - NLB) * 256 + r * 16 + c;
+      inc[i] = NBT * 256;
     }
-  };
-  // registers -> LDS buffer `buf` (same index walk as fetch); the row
-  // panels negated
-  auto stage = [&](double* buf) {
-    if (tid < NBT * 128)
-      *reinterpret_cast<f64x2*>(buf + (NLB + (tid >> 7)) * DL_BLK +
-                                ((tid >> 3) & 15) * DL_BS + 2 * (tid & 7)) =
-          pre[0];
+  }
+  const int wvu = __builtin_amdgcn_readfirstlane(wv);
+  auto dma = [&](double* buf) {
 #pragma unroll
-    for (int rb = 1; rb < NBT; ++rb) {
-      if (tid < rb * 128) {
-        const int r = tid / (rb * 8), c = 2 * (tid % (rb * 8));
-        *reinterpret_cast<f64x2*>(buf +
-                                  (rb * (rb - 1) / 2 + (c >> 4)) * DL_BLK +
-                                  r * DL_BS + (c & 15)) = -pre[rb];
-      }
+    for (int i = 0; i < NPT; ++i) {
+      if (512 * (i + 1) <= NP || tid + 512 * i < NP)
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) void*)src[i],
+            (__attribute__((address_space(3))) void*)(buf +
+                                                      2 * (512 * i + 64 * wvu)),
+            16, 0, 0);
+      src[i] += inc[i];
     }
   };
 
-  fetch(dlo);
+  dma(S);
 
   // this wave's RHS strip, acc layout, kept for the whole slice:
   // R0[rt][v] = RHS[row = rt*16 + 4v + lk][block-col jw + li]
@@ -942,19 +951,19 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
   // the lane that closes frequency q
   const bool closer = lk == 0 && (li & 1) == 0 && q < DL_FREQS && f < F;
 
-  stage(S);
-  __syncthreads();
+  __syncthreads();  // waits for the direct loads of draw dlo
 
   const int aoff = li * DL_BS + lk;  // a-fragment offset inside a block
   for (int d = dlo; d < dhi; ++d) {
     const int b = (d - dlo) & 1;
     const double* Sb = S + b * BUF;
     double* Wu = S + 2 * BUF + b * mp;
-    const bool more = d + 1 < dhi;
-    if (more) fetch(d + 1);
+    // every wave is past the barrier that ended the reads of buffer
+    // b ^ 1; the loads are waited for in front of this draw's barrier
+    if (d + 1 < dhi) dma(S + (b ^ 1) * BUF);
 
     // blocked forward substitution from the register RHS copy; acc is
-    // the negative of trsm_fp_kernel's (negated panels)
+    // the negative of trsm_fp_kernel's (the MFMA negates the panels)
     f64x4 W[NBT];
     double a1 = 0, a2 = 0, a3 = 0;
 #pragma unroll
@@ -969,9 +978,9 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
           const double a =
               Sb[(rb * (rb - 1) / 2 + cb) * DL_BLK + kk * 4 + aoff];
           if (cb & 1)
-            acc2 = MFMA_F64(a, W[cb][kk], acc2);
+            acc2 = MFMA_F64_NEGA(a, W[cb][kk], acc2);
           else
-            acc = MFMA_F64(a, W[cb][kk], acc);
+            acc = MFMA_F64_NEGA(a, W[cb][kk], acc);
         }
       }
       acc += acc2;
@@ -1001,7 +1010,6 @@ __global__ __launch_bounds__(512, 4) void trsm_fp_draws_kernel(
 #pragma unroll
         for (int v = 0; v < 4; ++v) Wu[rt * 16 + 4 * v + lk] = W[rt][v];
     }
-    if (more) stage(S + (b ^ 1) * BUF);
     // factor d+1 and u column d visible; every read of buffer b done
     __syncthreads();
 
