@@ -753,10 +753,57 @@ class FpEngine:
                 out.zero_()
             ext.trsm_fp_accum(*args)
 
-    def _pipeline_chunks(self, sy: SolveSystem, diag, chunks):
+    def _rows_in_place(self, sy: SolveSystem, rows):
+        """``(row0, pstride, var0)`` when the factor of the stacked
+        ``sy`` can read its diagonal from ``rows`` where they lie
+        (``chol_rows_into``), None otherwise.
+
+        That takes the per-pulsar (D, m) ``rows`` to be regular views of
+        ONE device tensor — same storage, same shape and strides, unit
+        column stride, pulsar p's view ``p * pstride`` elements behind
+        pulsar 0's ``row0``, which is what ``noise.batch_phiinv``
+        returns — every pulsar's ``var`` to be the same contiguous
+        column range of them (``var0`` its first column), and the
+        system to factor in the LDS-resident kernel.  Host-side pointer
+        and stride comparisons only: no sync, nothing launched."""
+        if (sy.A.dim() != 3 or not isinstance(rows, (list, tuple))
+                or len(rows) != sy.A.shape[0]
+                or ops.pad16(sy.A.shape[-1]) > ops.MAX_MP_CHOL):
+            return None
+        r0 = rows[0]
+        if (not r0.is_cuda or r0.dtype != torch.float64 or r0.dim() != 2
+                or (r0.shape[1] > 1 and r0.stride(1) != 1)):
+            return None
+        D, width = r0.shape
+        if not all(isinstance(v, slice) for v in sy.var):
+            return None
+        spans = {v.indices(width) for v in sy.var}
+        if len(spans) != 1:
+            return None
+        (var0, stop, step), = spans
+        if step != 1 or stop - var0 != sy.A.shape[-1] - sy.lead:
+            return None
+        base = r0.untyped_storage().data_ptr()
+        pstride = 0
+        for i, r in enumerate(rows[1:], 1):
+            if (r.dtype != r0.dtype or r.shape != r0.shape
+                    or r.untyped_storage().data_ptr() != base
+                    or (width > 1 and r.stride(1) != 1)
+                    or (D > 1 and r.stride(0) != r0.stride(0))):
+                return None
+            off = r.storage_offset() - r0.storage_offset()
+            if i == 1:
+                pstride = off
+            if pstride < 0 or off != i * pstride:
+                return None
+        return r0, pstride, var0
+
+    def _pipeline_chunks(self, sy: SolveSystem, factor_into, chunks):
         """``(lo, hi, L, invd)`` per draw chunk of a stacked system
         within ``MAX_MP_CHOL``, from a factor/solve software pipeline
-        with PING-PONG factor buffers and two-way event fencing.
+        with PING-PONG factor buffers and two-way event fencing;
+        ``factor_into(lo, hi, L, invd)`` launches the factor of the
+        draws [lo, hi) into the buffers.
 
         Chunk k+1's factor (side stream, buffer (k+1)&1) overlaps chunk
         k's solve, which the consumer queues on the main stream before
@@ -793,8 +840,7 @@ class FpEngine:
             with torch.cuda.stream(side):
                 if solve_done[b] is not None:
                     side.wait_event(solve_done[b])
-                self._ext.chol_batch_into(sy.A, diag(lo, hi), mp,
-                                          Lb[b][:n], Ib[b][:n])
+                factor_into(lo, hi, Lb[b][:n], Ib[b][:n])
                 ev = torch.cuda.Event()
                 ev.record(side)
             return ev
@@ -821,22 +867,51 @@ class FpEngine:
         ((P,) D, 5, F); otherwise (stacked only) the chunk's per-pulsar
         Fp planes are summed, deterministically by torch, into ``out``
         (D, F)."""
-        if sy.A.dim() == 3:  # gathered and stacked once: (P, D, m_var)
-            pinv = torch.stack([p[:, v] for p, v in zip(rows, sy.var)])
+        mp = ops.pad16(sy.A.shape[-1])
+        inrows = self._rows_in_place(sy, rows)
+        if inrows is not None:
+            # the factor reads the prior rows where they lie: no gathered
+            # copy, no diagonal kernels in front of a factor launch
+            row0, pstride, var0 = inrows
+            lead_dims, D = (sy.A.shape[0],), row0.shape[0]
+
+            def factor_into(lo, hi, L, invd):
+                self._ext.chol_rows_into(sy.A, row0, pstride, lo, hi - lo,
+                                         var0, sy.delta0, sy.lead, mp, L,
+                                         invd)
+
+            def factor(lo, hi):
+                n = sy.A.shape[0] * (hi - lo)
+                L = torch.empty((n, mp, mp), dtype=torch.float64,
+                                device=self.device)
+                invd = torch.empty((n, mp // 16, 16, 16),
+                                   dtype=torch.float64, device=self.device)
+                factor_into(lo, hi, L, invd)
+                return L, invd
         else:
-            pinv = rows[:, sy.var]
-        D = pinv.shape[-2]
+            if sy.A.dim() == 3:  # gathered and stacked once: (P, D, m_var)
+                pinv = torch.stack([p[:, v] for p, v in zip(rows, sy.var)])
+            else:
+                pinv = rows[:, sy.var]
+            lead_dims, D = tuple(pinv.shape[:-2]), pinv.shape[-2]
+
+            def diag(lo, hi):
+                return sy.diag(pinv[..., lo:hi, :]).contiguous()
+
+            def factor_into(lo, hi, L, invd):
+                self._ext.chol_batch_into(sy.A, diag(lo, hi), mp, L, invd)
+
+            def factor(lo, hi):
+                return ops.chol_factor(sy.A, diag(lo, hi), ext=self._ext)
+
         chunks = [(lo, min(lo + draw_chunk, D))
                   for lo in range(0, D, draw_chunk)]
         if not chunks:
             return
 
-        def diag(lo, hi):
-            return sy.diag(pinv[..., lo:hi, :]).contiguous()
-
         def empty(n):  # what the solve writes for n draws
             return torch.empty(
-                pinv.shape[:-2] + (n,) + out.shape[-2 if prods else -1:],
+                lead_dims + (n,) + out.shape[-2 if prods else -1:],
                 dtype=torch.float64, device=self.device)
 
         # SOFTWARE PIPELINE across the chunks of a stacked Fp sweep:
@@ -848,13 +923,10 @@ class FpEngine:
         # the pipeline hides the other fifth (docs/TUNING_NOTES.md).
         # Above MAX_MP_CHOL the factor is rocSOLVER's, which does not
         # write into caller buffers.
-        if (pipeline and len(chunks) > 1
-                and ops.pad16(sy.A.shape[-1]) <= ops.MAX_MP_CHOL):
-            factors = self._pipeline_chunks(sy, diag, chunks)
+        if pipeline and len(chunks) > 1 and mp <= ops.MAX_MP_CHOL:
+            factors = self._pipeline_chunks(sy, factor_into, chunks)
         else:
-            factors = ((lo, hi, *ops.chol_factor(sy.A, diag(lo, hi),
-                                                 ext=self._ext))
-                       for lo, hi in chunks)
+            factors = ((lo, hi, *factor(lo, hi)) for lo, hi in chunks)
         n0 = chunks[0][1]
         # products go straight into `out` where its draw slices are
         # contiguous (one pulsar, or a single chunk); otherwise through

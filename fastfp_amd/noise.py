@@ -410,19 +410,43 @@ def batch_phiinv(containers: list, pars: dict, homogeneous: bool = None):
     c0 = containers[0]
 
     dev = c0.Ffreqs.device
-    Ff = c0.Ffreqs
     gam = torch.stack(
         [_as_tensor(pars[c.rn_gam_name], dev).reshape(-1) for c in containers]
     )  # (P, D)
     lgA = torch.stack(
         [_as_tensor(pars[c.rn_A_name], dev).reshape(-1) for c in containers]
     )
-    P, D = gam.shape
+    out = None
+    if dev.type == "cuda":
+        from fastfp_amd import ops
+
+        out = ops.phi_inv_batch(c0, gam, lgA, pars, 1.0 / TM_PRIOR)
+    if out is None:
+        out = _batch_phiinv_torch(c0, gam, lgA, pars)
+    return [out[i] for i in range(out.shape[0])]
+
+
+def _bin_widths(Ff: torch.Tensor) -> torch.Tensor:
+    """Frequency-bin widths of a pairwise-repeated grid ``Ff`` (nf,),
+    repeated pairwise as well."""
     funique = Ff[::2]
     df = torch.diff(
-        torch.cat([torch.zeros(1, dtype=Ff.dtype, device=dev), funique])
+        torch.cat([torch.zeros(1, dtype=Ff.dtype, device=Ff.device), funique])
     )
-    dff = torch.repeat_interleave(df, 2)
+    return torch.repeat_interleave(df, 2)
+
+
+def _batch_phiinv_torch(c0, gam, lgA, pars: dict) -> torch.Tensor:
+    """The homogeneous phi^-1 (P, D, m) of :func:`batch_phiinv` as a
+    chain of torch ops, for the (P, D) red-noise parameters ``gam`` and
+    ``lgA`` of containers like ``c0``: the path of the CPU and of a
+    missing HIP extension, and the oracle of the HIP kernel
+    (``ops.phi_inv_batch``), which repeats its operations one rounding
+    at a time."""
+    dev = c0.Ffreqs.device
+    Ff = c0.Ffreqs
+    P, D = gam.shape
+    dff = _bin_widths(Ff)
     phi_rn = (
         Ff[None, None, :] ** (-gam[:, :, None])
         * (10.0 ** lgA[:, :, None]) ** 2
@@ -443,6 +467,6 @@ def batch_phiinv(containers: list, pars: dict, homogeneous: bool = None):
     )
     out[:, :, :ntm] = 1.0 / TM_PRIOR
     out[:, :, ntm:] = 1.0 / phi_rn
-    return [out[i] for i in range(P)]
+    return out
 
 

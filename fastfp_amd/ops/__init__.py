@@ -179,6 +179,68 @@ def chol_factor(TNT, phiinv, ext=None):
     return L, invd
 
 
+def _grid_widths(cont):
+    """``cont.Ffreqs`` contiguous and its pairwise bin widths, kept on the
+    container while ``Ffreqs`` is the same unmodified tensor (the grid
+    of a container is fixed; ``to(device)`` rebinds it)."""
+    from fastfp_amd.noise import _bin_widths
+
+    Ff = cont.Ffreqs
+    key = (Ff.data_ptr(), Ff._version, Ff.device, tuple(Ff.shape))
+    cached = getattr(cont, "_grid_widths", None)
+    if cached is None or cached[0] != key:
+        Fc = Ff.contiguous()
+        cached = (key, Fc, _bin_widths(Fc).contiguous())
+        cont._grid_widths = cached
+    return cached[1], cached[2]
+
+
+def phi_inv_batch(c0, gam, lgA, pars, tm_inv):
+    """The homogeneous prior phi^-1 of ``noise.batch_phiinv`` in ONE
+    kernel on the current stream: ``(P, D, ntm + nf)`` for the (P, D)
+    device tensors ``gam``/``lgA`` of red-noise containers like ``c0``
+    (with ``c0``'s common process from ``pars``), the timing-model
+    columns set to ``tm_inv``.  Nothing but the output is allocated, so
+    the call captures into a hipGraph.
+
+    Returns None — the caller runs its torch chain — when the extension
+    is not built or the common process's parameters are neither scalars
+    nor one per draw."""
+    ext = _try_load()
+    if ext is None:
+        return None
+    import numpy as np
+
+    from fastfp_amd.constants import fyr
+    from fastfp_amd.noise import _as_tensor
+
+    dev = gam.device
+    P, D = gam.shape
+    Ff, dff = _grid_widths(c0)
+    if Ff.device != dev or Ff.numel() % 2:
+        return None
+    common = (None, None, None, None)
+    if c0.add_curn:
+        cc = c0.curn_container
+        gc = _as_tensor(pars[cc.rn_gam_name], dev).reshape(-1).contiguous()
+        lc = _as_tensor(pars[cc.rn_A_name], dev).reshape(-1).contiguous()
+        Fc, dfc = _grid_widths(cc)
+        if (gc.numel() != lc.numel() or gc.numel() not in (1, D)
+                or Fc.device != dev or Fc.numel() > Ff.numel()):
+            return None
+        common = (gc, lc, Fc, dfc)
+    ntm = c0.tm_weights.shape[0]
+    out = torch.empty((P, D, ntm + Ff.numel()), dtype=torch.float64,
+                      device=dev)
+    # x / 12.0 and x / pi**2 of the torch chain are multiplications by
+    # the rounded reciprocal of the scalar: the kernel takes those
+    ext.phi_inv_batch(gam.contiguous(), lgA.contiguous(), common[0],
+                      common[1], Ff, dff, common[2], common[3], ntm,
+                      float(fyr), 1.0 / 12.0, 1.0 / np.pi**2, float(tm_inv),
+                      out)
+    return out
+
+
 def chol_trsm_fp_accum(TNT, phiinv, RHS, sNs, sNr, fp_out, gsign=1.0):
     """:func:`chol_factor`, then the fused triangular solve of RHS
     (mp, 2F+1) + 2x2 Fp reduction, accumulating into fp_out (D, F).

@@ -7,6 +7,8 @@
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
 
+#include <climits>
+
 #include "launchers.h"
 
 namespace {
@@ -108,6 +110,116 @@ void chol_batch_into(torch::Tensor TNT, torch::Tensor phiinv, int64_t mp,
                         (int)mp, D, P, L.data_ptr<double>(),
                         invd.data_ptr<double>(), stream()),
       "chol_batch");
+}
+
+// chol_rows_into: chol_batch_into with the diagonal read where the phi
+// assembly left it.  `row0` is pulsar 0's (D_all, width) view of the prior
+// rows (unit column stride); pulsar p's view lies `pstride` elements
+// further per pulsar in the same storage.  The factor takes draws
+// [d0, d0 + D) and columns [var0, var0 + m - lead) of it: the diagonal is
+// 0 on the `lead` leading identity rows of TNT (P,m,m) and behind them
+// the row entry, or 1 / (entry - delta0[p]) with delta0 (P, m-lead) given.
+// TNT = blockdiag(I_lead, G): the factor relies on that identity block
+// (launchers.h).
+void chol_rows_into(torch::Tensor TNT, torch::Tensor row0, int64_t pstride,
+                    int64_t d0, int64_t D, int64_t var0,
+                    c10::optional<torch::Tensor> delta0, int64_t lead,
+                    int64_t mp, torch::Tensor L, torch::Tensor invd) {
+  check_f64(TNT, "TNT");
+  check_f64(L, "L");
+  check_f64(invd, "invd");
+  TORCH_CHECK(TNT.dim() == 3, "TNT must be (P,m,m)");
+  TORCH_CHECK(row0.is_cuda() && row0.scalar_type() == torch::kFloat64 &&
+                  row0.dim() == 2 && (row0.size(1) <= 1 || row0.stride(1) == 1),
+              "row0 must be a (D,width) fp64 GPU view with unit column stride");
+  const int64_t P = TNT.size(0), m = TNT.size(1);
+  const int64_t mv = m - lead;
+  TORCH_CHECK(TNT.size(2) == m, "TNT must be square");
+  TORCH_CHECK(lead >= 0 && mv >= 0, "lead");
+  TORCH_CHECK(mp % 16 == 0 && mp >= 16 && mp <= 128 && mp >= m, "mp");
+  TORCH_CHECK(D >= 0 && d0 >= 0 && d0 + D <= row0.size(0), "draw range");
+  TORCH_CHECK(var0 >= 0 && var0 + mv <= row0.size(1), "column range");
+  TORCH_CHECK(pstride >= 0, "pstride");
+  TORCH_CHECK(L.size(0) == P * D && L.size(1) == mp && L.size(2) == mp,
+              "L shape");
+  TORCH_CHECK(invd.size(0) == P * D && invd.size(1) == mp / 16, "invd shape");
+  if (D == 0 || P == 0) return;  // empty batch: nothing to factor
+  const int64_t dstride = row0.stride(0);
+  TORCH_CHECK(dstride >= 0, "row0 draw stride");
+  // the last element the kernel reads must lie inside row0's storage
+  const int64_t last = row0.storage_offset() + (P - 1) * pstride +
+                       (d0 + D - 1) * dstride + var0 + mv - 1;
+  TORCH_CHECK(mv == 0 ||
+                  (last + 1) * (int64_t)sizeof(double) <=
+                      (int64_t)row0.storage().nbytes(),
+              "prior rows reach past their storage");
+  const double* dl = nullptr;
+  if (delta0.has_value()) {
+    check_f64(*delta0, "delta0");
+    TORCH_CHECK(delta0->dim() == 2 && delta0->size(0) == P &&
+                    delta0->size(1) == mv, "delta0 must be (P, m-lead)");
+    dl = delta0->data_ptr<double>();
+  }
+  check_launch(
+      launch_chol_rows(TNT.data_ptr<double>(),
+                       row0.data_ptr<double>() + d0 * dstride + var0, pstride,
+                       dstride, dl, (int)lead, (int)m, (int)mp, (int)D, (int)P,
+                       L.data_ptr<double>(), invd.data_ptr<double>(), stream()),
+      "chol_rows");
+}
+
+// phi_inv_batch: gam, lgA (P,D); the common process gam_c, lgA_c (D,) or
+// (1,) on the bins Ff_c, dff_c (nc,) (all four absent: no common
+// process); Ff, dff (nf,) -> out (P,D,ntm+nf), every entry written.
+void phi_inv_batch(torch::Tensor gam, torch::Tensor lgA,
+                   c10::optional<torch::Tensor> gam_c,
+                   c10::optional<torch::Tensor> lgA_c, torch::Tensor Ff,
+                   torch::Tensor dff, c10::optional<torch::Tensor> Ff_c,
+                   c10::optional<torch::Tensor> dff_c, int64_t ntm, double fyr,
+                   double inv12, double invpi2, double tm_inv,
+                   torch::Tensor out) {
+  check_f64(gam, "gam");
+  check_f64(lgA, "lgA");
+  check_f64(Ff, "Ff");
+  check_f64(dff, "dff");
+  check_f64(out, "out");
+  TORCH_CHECK(gam.dim() == 2 && lgA.sizes() == gam.sizes(),
+              "gam, lgA must be (P,D)");
+  const int64_t P = gam.size(0), D = gam.size(1), nf = Ff.numel();
+  TORCH_CHECK(Ff.dim() == 1 && dff.dim() == 1 && dff.numel() == nf &&
+                  nf % 2 == 0, "Ff, dff must be (nf,), nf even");
+  TORCH_CHECK(ntm >= 0 && out.dim() == 3 && out.size(0) == P &&
+                  out.size(1) == D && out.size(2) == ntm + nf, "out shape");
+  TORCH_CHECK(P * D <= INT_MAX && ntm + nf <= INT_MAX / 64, "size");
+  int64_t nc = 0, cstride = 0;
+  const double *gc = nullptr, *lc = nullptr, *fc = nullptr, *dc = nullptr;
+  if (gam_c.has_value()) {
+    TORCH_CHECK(lgA_c.has_value() && Ff_c.has_value() && dff_c.has_value(),
+                "the common process needs gam_c, lgA_c, Ff_c and dff_c");
+    check_f64(*gam_c, "gam_c");
+    check_f64(*lgA_c, "lgA_c");
+    check_f64(*Ff_c, "Ff_c");
+    check_f64(*dff_c, "dff_c");
+    nc = Ff_c->numel();
+    TORCH_CHECK(Ff_c->dim() == 1 && dff_c->dim() == 1 &&
+                    dff_c->numel() == nc && nc <= nf, "Ff_c, dff_c (nc <= nf)");
+    const int64_t n = gam_c->numel();
+    TORCH_CHECK(gam_c->dim() == 1 && lgA_c->dim() == 1 &&
+                    lgA_c->numel() == n && (n == D || n == 1),
+                "gam_c, lgA_c must be (D,) or (1,)");
+    cstride = (n == 1) ? 0 : 1;
+    gc = gam_c->data_ptr<double>();
+    lc = lgA_c->data_ptr<double>();
+    fc = Ff_c->data_ptr<double>();
+    dc = dff_c->data_ptr<double>();
+  }
+  check_launch(
+      launch_phi_inv_batch(gam.data_ptr<double>(), lgA.data_ptr<double>(), gc,
+                           lc, (int)cstride, Ff.data_ptr<double>(),
+                           dff.data_ptr<double>(), fc, dc, (int)nf, (int)nc,
+                           (int)ntm, (int)P, (int)D, fyr, inv12, invpi2, tm_inv,
+                           out.data_ptr<double>(), stream()),
+      "phi_inv_batch");
 }
 
 // chol_batch: allocate L/invd and factor into them.
@@ -494,6 +606,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("chol_batch", &chol_batch, "batched LDS-resident fp64 Cholesky");
   m.def("chol_batch_into", &chol_batch_into,
         "chol_batch into caller-owned L/invd (pipeline buffers)");
+  m.def("chol_rows_into", &chol_rows_into,
+        "chol_batch_into with the diagonal read from strided prior rows",
+        py::arg("TNT"), py::arg("row0"), py::arg("pstride"), py::arg("d0"),
+        py::arg("D"), py::arg("var0"), py::arg("delta0"), py::arg("lead"),
+        py::arg("mp"), py::arg("L"), py::arg("invd"));
+  m.def("phi_inv_batch", &phi_inv_batch,
+        "homogeneous prior phi^-1 (P,D,ntm+nf) in one kernel");
   m.def("trsm_fp_accum", &trsm_fp_accum,
         "batched TRSM + fused 2x2 Fp reduction");
   m.def("trsm_fp_store", &trsm_fp_store,

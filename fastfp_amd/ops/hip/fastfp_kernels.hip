@@ -19,7 +19,12 @@
 //                        assembled in LDS (never materialized in HBM),
 //                        MFMA trailing updates, inverted 16x16 diagonal
 //                        blocks exported for the solver (subsumes
-//                        utils.py:76 + the LU in utils.py:54)
+//                        utils.py:76 + the LU in utils.py:54); the
+//                        diagonal comes as a (P,D,m) tensor or is formed
+//                        from the strided prior rows in place
+//   phi_inv_batch_kernel — the homogeneous prior phi^-1 (P,D,ntm+nf)
+//                        from the power-law parameters in one pass, bit
+//                        for bit the torch chain of noise.batch_phiinv
 //   trsm_fp_kernel     — batched blocked forward-substitution
 //                        W = L^-1 [B | TNr] fused with the per-frequency
 //                        2x2 Gram/solve/Fp reduction; W lives entirely
@@ -43,7 +48,8 @@
 // extern "C" launcher per kernel, and two for the solve, each taking an
 // `int prods` — launch_trsm (trsm_fp_kernel, trsm_fp_rl_kernel) over
 // launch_one_draw<PRODS>, launch_trsm_draws (trsm_fp_draws_kernel) over
-// launch_draws<PRODS>.
+// launch_draws<PRODS> — and two for the factor, launch_chol_batch and
+// launch_chol_rows over chol_dispatch.
 //
 // Each launcher below is one dispatch: there are no environment-
 // selected variants.  The alternatives that were tried and measured
@@ -293,16 +299,29 @@ static __device__ __forceinline__ double row_bcast(double w, int t) {
   return __hiloint2double(hi, lo);
 }
 
-template <int NBT>
+// T0 (0, 4, 8 or 12): the first T0 rows and columns of Sigma are known
+// to be an exact identity block (the leading pad of the stacked
+// compressed system, T0 <= lead), and diagonal block 0 leaves out the
+// steps that would factor and invert it.
+template <int NBT, int T0 = 0>
 __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     const double* __restrict__ TNT_all /*(P,m,m)*/,
     const double* __restrict__ phiinv_all /*(P,D,m)*/, int m, int D,
     double* __restrict__ L_all /*(P*D,mp,mp)*/,
-    double* __restrict__ invd_all /*(P*D, mp/16, 16, 16)*/) {
+    double* __restrict__ invd_all /*(P*D, mp/16, 16, 16)*/,
+    // second diagonal source (phiinv_all null): the prior rows where
+    // the phi assembly left them.  Entry (p, d, i) is at
+    // rows_all[p * rows_ps + d * rows_ds + i]; the diagonal is 0 on the
+    // `lead` leading identity rows of TNT and behind them, for i < m -
+    // lead, rows[i] (delta0_all null) or 1 / (rows[i] - delta0[p][i])
+    const double* __restrict__ rows_all, long rows_ps, long rows_ds,
+    const double* __restrict__ delta0_all /*(P, m-lead)*/, int lead) {
   // grid.y batches PULSARS: one launch factors every (pulsar, draw)
   const int pp = blockIdx.y;
   const double* TNT = TNT_all + (long)pp * m * m;
   const double* phiinv = phiinv_all + (long)pp * D * m;
+  const double* rows = rows_all + (long)pp * rows_ps;
+  const double* delta0 = delta0_all + (long)pp * (m - lead);
   double* L = L_all + (long)pp * D * (NBT * 16) * (NBT * 16);
   double* invd = invd_all + (long)pp * D * NBT * 256;
   // LDS is sized by the template so small matrices keep multiple
@@ -322,13 +341,40 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
 
   const int nthr = blockDim.x;
   const int nwv = nthr >> 6;
+  // From the prior rows, the diagonal is the last mp threads', one entry
+  // each: they load ahead of the assembly loop and divide behind it.
+  // (The division inside the loop ran in every wave on every pass, a
+  // diagonal entry being 65 apart: +8% on the isolated factor.)
+  const bool inrows = phiinv_all == nullptr;
+  const int di = inrows ? tid - (nthr - mp) : -1;
+  double dtnt = 0.0, dsrc = 0.0, dsub = 0.0;
+  if (di >= 0 && di < m) {
+    dtnt = TNT[(long)di * m + di];
+    if (di >= lead) {
+      dsrc = rows[(long)d * rows_ds + (di - lead)];
+      if (delta0_all != nullptr) dsub = delta0[di - lead];
+    }
+  }
   // assemble Sigma in LDS (lower triangle only)
   for (int idx = tid; idx < mp * mp; idx += nthr) {
     const int i = idx / mp, j = idx % mp;
     if (j > i) continue;
     double v = (i < m && j < m) ? TNT[(long)i * m + j] : 0.0;
-    if (i == j) v += (i < m) ? phiinv[(long)d * m + i] : 1.0;
+    if (i == j) {
+      if (inrows) continue;
+      v += (i < m) ? phiinv[(long)d * m + i] : 1.0;
+    }
     A_(i, j) = v;
+  }
+  if (di >= 0) {
+    // SolveSystem.diag's operations in its order; the division is
+    // correctly rounded, as torch's reciprocal is
+    double dg = 1.0;  // the identity pad behind m
+    if (di < lead)
+      dg = 0.0;
+    else if (di < m)
+      dg = (delta0_all != nullptr) ? 1.0 / (dsrc - dsub) : dsrc;
+    A_(di, di) = dtnt + dg;
   }
   __syncthreads();
 
@@ -351,14 +397,22 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
   // finite lrt and the t >= c select is not needed.  The entries that
   // are used see the same operations in the same order as under the
   // selects: L and invd keep every bit.
-#define CHOL_DIAG(KB, DST)                                                   \
+  //
+  // TS > 0 (diagonal block 0 under T0): rows and columns < TS of the
+  // block are an exact identity.  Steps t < TS of the factorisation are
+  // sqrt(1), divisions by 1 and updates with an exact zero factor, rows
+  // r < TS of the inversion are unit vectors and the terms t < TS of
+  // the later rows multiply an exact zero of L: all left out.  Every
+  // value keeps its bits except exact zeros of invd below the diagonal
+  // in columns < TS, -0.0 from the full chain and +0.0 here.
+#define CHOL_DIAG(KB, DST, TS)                                               \
   {                                                                          \
     const int dk0 = (KB)*NB;                                                 \
     const int i = lane & 15;                                                 \
     double row[16];                                                          \
     _Pragma("unroll") for (int c = 0; c < 16; ++c) row[c] =                  \
         AS_(dk0 + i, dk0 + c);                                               \
-    _Pragma("unroll") for (int t = 0; t < 16; ++t) {                         \
+    _Pragma("unroll") for (int t = (TS); t < 16; ++t) {                      \
       const double dv = sqrt(row_bcast(row[t], t));                          \
       double rdv = 1.0 / dv;                                                 \
       /* every lane divides: a division kept to the lanes i != t is a  */   \
@@ -382,10 +436,12 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     double dii = 0.0;                                                        \
     _Pragma("unroll") for (int r = 0; r < 16; ++r) if (r == i) dii = row[r]; \
     const double myrcp = 1.0 / dii;                                          \
-    _Pragma("unroll") for (int r = 0; r < 16; ++r) {                         \
+    _Pragma("unroll") for (int r = 0; r < (TS); ++r)                         \
+        x[r] = (r == c) ? 1.0 : 0.0;                                         \
+    _Pragma("unroll") for (int r = (TS); r < 16; ++r) {                      \
       const double dr = row_bcast(myrcp, r);                                 \
       double acc2 = 0.0;                                                     \
-      _Pragma("unroll") for (int t = 0; t < 16; ++t) {                       \
+      _Pragma("unroll") for (int t = (TS); t < 16; ++t) {                    \
         const double lrt = row_bcast(row[t], r);                             \
         if (t < r) acc2 = fma(lrt, x[t], acc2);                              \
       }                                                                      \
@@ -399,7 +455,7 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
   }
 
   // prologue: factor + invert diagonal block 0
-  if (wv == 0) CHOL_DIAG(0, inv16[0]);
+  if (wv == 0) CHOL_DIAG(0, inv16[0], T0);
   __syncthreads();
 
   for (int kb = 0; kb < nb; ++kb) {
@@ -453,7 +509,7 @@ __global__ __launch_bounds__(512, 4) void chol_batch_kernel(
     // slower with the DPP chain — docs/TUNING_NOTES.md — and is not
     // built.)
     if (wv == 0) {
-      CHOL_DIAG(kb + 1, inv16[(kb + 1) & 1]);
+      CHOL_DIAG(kb + 1, inv16[(kb + 1) & 1], 0);
     } else {
       const int t = nb - kb - 2;
       const int ntile = t * (t + 1) / 2;
@@ -1431,6 +1487,93 @@ static int launch_one_draw(const double* L, const double* invd,
 }
 
 // ---------------------------------------------------------------------
+// phi_inv_batch: the homogeneous prior phi^-1 of noise.batch_phiinv in
+// one pass — out (P, D, ntm + nf), every entry written:
+//   out[p, d, :ntm]     = tm_inv
+//   out[p, d, ntm + k]  = 1 / (phi_rn[p, d, k] (+ phi_c[d, k], k < nc))
+//   phi = f_k^-gam * (10^lgA)^2 * (1/12) * (1/pi^2) * fyr^(gam-3) * dff_k
+// with the products in exactly this order and one rounding each (no
+// FMA contraction), the operations of the torch chain the kernel
+// replaces, so the result matches it bit for bit wherever the device
+// pow is torch's.  A workgroup takes PHI_ROWS consecutive (p, d) rows:
+// it first computes the per-row factors (10^lgA)^2 and fyr^(gam-3) of
+// the red noise and of the common process once into LDS, then walks the
+// rows' entries, a sine/cosine pair per thread — the two bins share
+// their frequency, so one pow serves both.
+// ---------------------------------------------------------------------
+#define PHI_ROWS 16
+
+extern "C" __global__ __launch_bounds__(256) void phi_inv_batch_kernel(
+    const double* __restrict__ gam /*(P*D)*/,
+    const double* __restrict__ lgA /*(P*D)*/,
+    const double* __restrict__ gam_c /*(D) at stride c_dstride; nc > 0*/,
+    const double* __restrict__ lgA_c, int c_dstride,
+    const double* __restrict__ Ff /*(nf)*/,
+    const double* __restrict__ dff /*(nf)*/,
+    const double* __restrict__ Ff_c /*(nc)*/,
+    const double* __restrict__ dff_c /*(nc)*/, int nf, int nc, int ntm,
+    long nrows, int D, double ten, double fyr, double inv12, double invpi2,
+    double tm_inv, double* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double s_ng[2][PHI_ROWS], s_a2[2][PHI_ROWS], s_fy[2][PHI_ROWS];
+  const int tid = threadIdx.x;
+  const long r0 = (long)blockIdx.x * PHI_ROWS;
+  const int nr = (int)min((long)PHI_ROWS, nrows - r0);
+
+  // per-row factors: threads [0, PHI_ROWS) the red noise of row r0 +
+  // tid, threads [PHI_ROWS, 2 PHI_ROWS) the common process of its draw
+  if (tid < 2 * PHI_ROWS) {
+    const int which = tid / PHI_ROWS, rl = tid % PHI_ROWS;
+    if (rl < nr && (which == 0 || nc > 0)) {
+      const long r = r0 + rl;
+      const long ci = (r % D) * c_dstride;
+      const double g = which ? gam_c[ci] : gam[r];
+      const double la = which ? lgA_c[ci] : lgA[r];
+      const double a = pow(ten, la);
+      s_ng[which][rl] = -g;
+      s_a2[which][rl] = a * a;
+      s_fy[which][rl] = pow(fyr, g - 3.0);
+    }
+  }
+  __syncthreads();
+
+  const int m = ntm + nf;
+  const int w = ntm + nf / 2;  // entries of a row: tm bins, then pairs
+  for (int idx = tid; idx < nr * w; idx += blockDim.x) {
+    const int rl = idx / w, it = idx % w;
+    double* o = out + (r0 + rl) * m;
+    if (it < ntm) {
+      o[it] = tm_inv;
+      continue;
+    }
+    const int k = 2 * (it - ntm);
+    double phi[2];
+    {
+      const double f0 = Ff[k], f1 = Ff[k + 1];
+      const double ng = s_ng[0][rl];
+      const double p0 = pow(f0, ng);
+      const double p1 = (f1 == f0) ? p0 : pow(f1, ng);
+      const double a2 = s_a2[0][rl], fy = s_fy[0][rl];
+      phi[0] = p0 * a2 * inv12 * invpi2 * fy * dff[k];
+      phi[1] = p1 * a2 * inv12 * invpi2 * fy * dff[k + 1];
+    }
+    if (k < nc) {
+      const int k1 = (k + 1 < nc) ? k + 1 : k;
+      const double f0 = Ff_c[k], f1 = Ff_c[k1];
+      const double ng = s_ng[1][rl];
+      const double p0 = pow(f0, ng);
+      const double p1 = (f1 == f0) ? p0 : pow(f1, ng);
+      const double a2 = s_a2[1][rl], fy = s_fy[1][rl];
+      phi[0] = phi[0] + p0 * a2 * inv12 * invpi2 * fy * dff_c[k];
+      if (k + 1 < nc)
+        phi[1] = phi[1] + p1 * a2 * inv12 * invpi2 * fy * dff_c[k1];
+    }
+    o[ntm + k] = 1.0 / phi[0];
+    o[ntm + k + 1] = 1.0 / phi[1];
+  }
+}
+
+// ---------------------------------------------------------------------
 // host-side launchers (called from bindings.cpp), declared in
 // launchers.h.  Each returns the hipError_t of its launch as an int
 // (0 = success); a solve dimension with no instantiation is
@@ -1458,23 +1601,73 @@ int launch_sbgemm(const double* T, const double* toas, const double* ninv,
   return (int)hipGetLastError();
 }
 
-int launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
-                      int D, int P, double* L, double* invd,
-                      hipStream_t stream) {
+// The factor's one dispatch: the diagonal from `phiinv` (P,D,m), or,
+// with `phiinv` null, from the strided prior rows (chol_batch_kernel).
+static int chol_dispatch(const double* TNT, const double* phiinv, int m,
+                         int mp, int D, int P, double* L, double* invd,
+                         const double* rows, long rows_ps, long rows_ds,
+                         const double* delta0, int lead,
+                         hipStream_t stream) {
   // small matrices: 256 threads, so that 5 workgroups per CU (the
   // ~95-VGPR diagonal factor allows 5 waves/SIMD) run their serial
   // chains side by side (128 threads, 7 per CU by LDS: within noise,
   // docs/TUNING_NOTES.md); large: 512 threads for MFMA coverage
   const dim3 grid(D, P), blk(mp <= 64 ? 256 : 512);
-  switch (mp >> 4) {
-#define CHOL_CASE(NBT) \
-    case NBT: hipLaunchKernelGGL((chol_batch_kernel<NBT>), grid, blk, \
-                  0, stream, TNT, phiinv, m, D, L, invd); break;
-    CHOL_CASE(1) CHOL_CASE(2) CHOL_CASE(3) CHOL_CASE(4)
-    CHOL_CASE(5) CHOL_CASE(6) CHOL_CASE(7) CHOL_CASE(8)
+  // the identity lead is the stacked compressed system's, mp <= 64;
+  // its whole 4-step groups are left out of diagonal block 0
+  const int t0 = (rows != nullptr && mp <= 64) ? std::min(lead, 15) / 4 : 0;
+  switch ((mp >> 4) | (t0 << 4)) {
+#define CHOL_CASE(NBT, T0) \
+    case NBT | ((T0 / 4) << 4): \
+      hipLaunchKernelGGL((chol_batch_kernel<NBT, T0>), grid, blk, 0, stream, \
+                         TNT, phiinv, m, D, L, invd, rows, rows_ps, rows_ds, \
+                         delta0, lead); break;
+    CHOL_CASE(1, 0) CHOL_CASE(2, 0) CHOL_CASE(3, 0) CHOL_CASE(4, 0)
+    CHOL_CASE(5, 0) CHOL_CASE(6, 0) CHOL_CASE(7, 0) CHOL_CASE(8, 0)
+    CHOL_CASE(1, 4) CHOL_CASE(2, 4) CHOL_CASE(3, 4) CHOL_CASE(4, 4)
+    CHOL_CASE(1, 8) CHOL_CASE(2, 8) CHOL_CASE(3, 8) CHOL_CASE(4, 8)
+    CHOL_CASE(1, 12) CHOL_CASE(2, 12) CHOL_CASE(3, 12) CHOL_CASE(4, 12)
 #undef CHOL_CASE
     default: return (int)hipErrorInvalidValue;
   }
+  return (int)hipGetLastError();
+}
+
+int launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
+                      int D, int P, double* L, double* invd,
+                      hipStream_t stream) {
+  return chol_dispatch(TNT, phiinv, m, mp, D, P, L, invd, nullptr, 0, 0,
+                       nullptr, 0, stream);
+}
+
+int launch_chol_rows(const double* TNT, const double* rows, long rows_ps,
+                     long rows_ds, const double* delta0, int lead, int m,
+                     int mp, int D, int P, double* L, double* invd,
+                     hipStream_t stream) {
+  if (rows == nullptr || lead < 0 || lead > m) return (int)hipErrorInvalidValue;
+  return chol_dispatch(TNT, nullptr, m, mp, D, P, L, invd, rows, rows_ps,
+                       rows_ds, delta0, lead, stream);
+}
+
+int launch_phi_inv_batch(const double* gam, const double* lgA,
+                         const double* gam_c, const double* lgA_c,
+                         int c_dstride, const double* Ff, const double* dff,
+                         const double* Ff_c, const double* dff_c, int nf,
+                         int nc, int ntm, int P, int D, double fyr,
+                         double inv12, double invpi2, double tm_inv,
+                         double* out, hipStream_t stream) {
+  if (nf < 0 || (nf & 1) || nc < 0 || nc > nf || ntm < 0 || P < 0 || D < 0)
+    return (int)hipErrorInvalidValue;
+  const long nrows = (long)P * D;
+  if (nrows == 0 || ntm + nf == 0) return 0;
+  const long nblk = (nrows + PHI_ROWS - 1) / PHI_ROWS;
+  if (nblk > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  // 10.0 and fyr are run-time values to the kernel, so no part of a
+  // pow folds at compile time
+  hipLaunchKernelGGL(phi_inv_batch_kernel, dim3((unsigned)nblk), dim3(256), 0,
+                     stream, gam, lgA, gam_c, lgA_c, c_dstride, Ff, dff, Ff_c,
+                     dff_c, nf, nc, ntm, nrows, D, 10.0, fyr, inv12, invpi2,
+                     tm_inv, out);
   return (int)hipGetLastError();
 }
 

@@ -41,6 +41,31 @@ int launch_chol_batch(const double* TNT, const double* phiinv, int m, int mp,
                       int D, int P, double* L, double* invd,
                       hipStream_t stream);
 
+// The same factor with the diagonal read from strided prior rows: entry
+// (p, d, i) at rows[p * rows_ps + d * rows_ds + i], i < m - lead.  The
+// diagonal added to TNT (P,m,m) is 0 on its `lead` leading identity rows
+// and behind them rows[i], or 1 / (rows[i] - delta0[p][i]) with delta0
+// (P, m-lead) not null.  TNT must carry the identity on those `lead` rows
+// and columns: for mp <= 64 the factor leaves their whole 4-step groups
+// out of diagonal block 0 instead of computing sqrt(1) and x * 0.
+int launch_chol_rows(const double* TNT, const double* rows, long rows_ps,
+                     long rows_ds, const double* delta0, int lead, int m,
+                     int mp, int D, int P, double* L, double* invd,
+                     hipStream_t stream);
+
+// Homogeneous prior phi^-1: gam, lgA (P,D); the common process gam_c,
+// lgA_c (one entry per draw, c_dstride apart; read only when nc > 0) on
+// its own bins Ff_c, dff_c (nc,), nc <= nf; Ff, dff (nf,), nf even ->
+// out (P,D,ntm+nf), the first ntm columns tm_inv.  inv12, invpi2: the
+// rounded reciprocals of 12 and pi^2 that the power law multiplies by.
+int launch_phi_inv_batch(const double* gam, const double* lgA,
+                         const double* gam_c, const double* lgA_c,
+                         int c_dstride, const double* Ff, const double* dff,
+                         const double* Ff_c, const double* dff_c, int nf,
+                         int nc, int ntm, int P, int D, double fyr,
+                         double inv12, double invpi2, double tm_inv,
+                         double* out, hipStream_t stream);
+
 // L (B,mp,mp) -> invd, nblk_total = B * mp/16 inverted diagonal blocks
 int launch_diag_inv(const double* L, int mp, long nblk_total, double* invd,
                     hipStream_t stream);

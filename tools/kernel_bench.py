@@ -198,6 +198,18 @@ def main_factor(P=67, D=1024, m=60):
     print(f"chol_batch_into P={P} D={D} mp={mp}: {t*1e3:9.3f} ms"
           f"  ({t/(P*D)*1e9:7.1f} ns/matrix,"
           f" {P*D*(mp*mp+mp*16)*8/t/1e9:7.1f} GB/s written)")
+    # the sweep's form: the lead-padded system, the diagonal read from
+    # the prior rows in place (1 / (rows - delta0) behind the lead)
+    lead = mp - m
+    A = torch.zeros((P, mp, mp), dtype=torch.float64, device=DEV)
+    A[:, :lead, :lead] = torch.eye(lead, dtype=torch.float64, device=DEV)
+    A[:, lead:, lead:] = TNT
+    delta0 = torch.full((P, m), 1e-3, dtype=torch.float64, device=DEV)
+    rows = 1.0 / phiinv + delta0[:, None, :]
+    t = timeit(lambda: ext.chol_rows_into(A, rows[0], rows.stride(0), 0, D,
+                                          0, delta0, lead, mp, L, invd),
+               iters=50, warmup=5)
+    print(f"chol_rows_into  P={P} D={D} mp={mp} lead={lead}: {t*1e3:9.3f} ms")
 
 
 def main_fe(P=67, D=256, F=200, nsky=768, m=120):

@@ -100,8 +100,12 @@ def main():
             pin.append(p[:, st.var[i]])
         return st.diag(torch.stack(pin)).contiguous()
 
+    # the step gathers only when the factor cannot read the rows in place
+    # (separate per-pulsar tensors); batch_phiinv's views need no gather
+    inrows = eng._rows_in_place(st, piv)
     t_gather = ev_time(gather)
-    print(f"pinv gather/recip: {t_gather*1e3:8.2f} ms")
+    print(f"pinv gather/recip: {t_gather*1e3:8.2f} ms"
+          + ("   (not in the step: rows read in place)" if inrows else ""))
 
     phi_var = gather()
     mp = ops.pad16(mv)
@@ -111,6 +115,12 @@ def main():
     t_chol = ev_time(lambda: ext.chol_batch(st.A, phi_var, mp))
     print(f"chol             : {t_chol*1e3:8.2f} ms")
     L, invd = ext.chol_batch(st.A, phi_var, mp)
+    if inrows:
+        row0, pstride, var0 = inrows
+        t_rows = ev_time(lambda: ext.chol_rows_into(
+            st.A, row0, pstride, 0, D, var0, st.delta0, st.lead, mp, L, invd))
+        print(f"chol, rows in place: {t_rows*1e3:6.2f} ms")
+        t_gather, t_chol = 0.0, t_rows
     pp = torch.zeros((P, D, F), dtype=torch.float64, device=DEV)
     t_trsm = ev_time(
         lambda: ext.trsm_fp_accum(L, invd, st.RHS, st.S, st.R, pp, -1.0)
