@@ -1,8 +1,8 @@
 """Earth-term Fe-statistic: sky-coherent continuous-wave detection.
 
-The reference lists this as an open to-do (``/root/reference/README.md:23``
-"Include Fe-statistic?") and never implemented it; this module completes
-that roadmap natively.  Where Fp maximizes a per-pulsar 2-amplitude
+The reference lists this as an open to-do (its README: "Include
+Fe-statistic?") and never implemented it; this module completes that
+roadmap natively.  Where Fp maximizes a per-pulsar 2-amplitude
 filter incoherently (one 2x2 solve per pulsar), Fe maximizes the
 EARTH-TERM signal coherently across the array (Ellis, Siemens &
 Creighton 2012): four sky-dependent filters
@@ -27,12 +27,15 @@ Fe map is therefore nearly free on top of an Fp sweep — the
 MI355X-native restructure of the statistic.
 
 Two assemblies exist.  The default (``assemble="host"``) takes the
-products from the torch path and solves the 4x4 systems in numpy.  On a
-HIP engine ``assemble="device"`` and ``sweep_max`` take the products
-from the HIP solve (``FpEngine.sweep_products_hip``) and run the sky
-assembly in the MFMA kernels ``ops.fe_assemble`` / ``ops.fe_skymax``;
-``sweep_max`` returns the statistic maximised over the sky with its
-argmax and never forms the (draws x sky x freqs) cube.
+products from the torch path and solves the 4x4 systems in numpy
+(:func:`_assemble_fe_draws`).  On a HIP engine ``assemble="device"`` and
+``sweep_max`` take the products from the HIP solve
+(``FpEngine.sweep_products_hip``) and run the sky assembly in the MFMA
+kernels ``ops.fe_assemble`` / ``ops.fe_skymax``; ``sweep_max`` returns
+the statistic maximised over the sky with its argmax and never forms the
+(draws x sky x freqs) cube.  :class:`FastFe` and :class:`NMFe` differ
+only in where the products (P, draws, 5, F) come from; the sky layer
+:class:`_Sky` under both chooses between the kernels and the host.
 
 The same solve yields the maximum-likelihood amplitudes ``a = M^-1 N``:
 ``sweep_max(amplitudes=True)`` returns them at the sky maximum and
@@ -57,7 +60,9 @@ import math
 import numpy as np
 import torch
 
+from fastfp_amd import ops
 from fastfp_amd.engine import FpEngine, _t64
+from fastfp_amd.noise import batch_phiinv
 from fastfp_amd.xcy import get_xCy
 
 
@@ -172,46 +177,64 @@ def _solve4(M, N, rcond):
                          for Mi, Ni in zip(flatM, flatN)]).reshape(N.shape)
 
 
-def _assemble_fe(prods, fplus, fcross, rcond=1e-12, amplitudes=False):
-    """Fe(f) from per-pulsar corrected products.
+def _psum(coeff, q):
+    """``sum_p coeff_p q_p``: (P,) x (P, ...) -> (...)."""
+    return np.einsum("p,p...->...", coeff, q)
 
-    ``prods``: (P, 5, F) array of [ss, cc, sc, sr, cr]; ``fplus`` /
-    ``fcross``: (P,) antenna coefficients.  Returns (F,), or with
-    ``amplitudes`` the pair ``(fe (F,), a (F, 4))`` with the
-    maximum-likelihood amplitudes ``a = M^-1 N``.
 
-    M is assembled per frequency from sums over pulsars and solved as
-    a 4x4 system; near-degenerate skies (e.g. all pulsars clustered:
-    F+/Fx columns collinear) go through the pseudo-inverse — the
-    maximized likelihood is well-defined on the column space.
-    """
-    ss, cc, sc = prods[:, 0, :], prods[:, 1, :], prods[:, 2, :]
-    sr, cr = prods[:, 3, :], prods[:, 4, :]
-    fp2 = fplus**2
-    fx2 = fcross**2
-    fpx = fplus * fcross
+# (row, column) of the ten unique entries of the symmetric 4x4 M
+_UPPER = [(i, j) for i in range(4) for j in range(i, 4)]
 
-    def w(coeff, q):  # sum_p coeff_p * q_p(f)  -> (F,)
-        return np.einsum("p,pf->f", coeff, q)
 
-    F = prods.shape[2]
-    M = np.empty((F, 4, 4))
-    M[:, 0, 0] = w(fp2, ss)
-    M[:, 0, 1] = M[:, 1, 0] = w(fp2, sc)
-    M[:, 0, 2] = M[:, 2, 0] = w(fpx, ss)
-    M[:, 0, 3] = M[:, 3, 0] = w(fpx, sc)
-    M[:, 1, 1] = w(fp2, cc)
-    M[:, 1, 2] = M[:, 2, 1] = w(fpx, sc)
-    M[:, 1, 3] = M[:, 3, 1] = w(fpx, cc)
-    M[:, 2, 2] = w(fx2, ss)
-    M[:, 2, 3] = M[:, 3, 2] = w(fx2, sc)
-    M[:, 3, 3] = w(fx2, cc)
-    N = np.stack(
-        [w(fplus, sr), w(fplus, cr), w(fcross, sr), w(fcross, cr)], axis=1
-    )  # (F, 4)
+def _moments(prods, fplus, fcross):
+    """The ten unique entries of ``M`` for one sky row, ``(m00, m01, m02,
+    m03, m11, m12, m13, m22, m23, m33)`` as in ``_UPPER``, each (D, F), from
+    the planes ss, cc, sc of ``prods`` (P, D, 5, F) and (P,) coefficients."""
+    ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
+    fp2, fx2, fpx = fplus**2, fcross**2, fplus * fcross
+    m03 = _psum(fpx, sc)  # = m12
+    return (_psum(fp2, ss), _psum(fp2, sc), _psum(fpx, ss), m03,
+            _psum(fp2, cc), m03, _psum(fpx, cc),
+            _psum(fx2, ss), _psum(fx2, sc), _psum(fx2, cc))
+
+
+def _full_m(moments):
+    """The symmetric ``M`` (..., 4, 4) from its ten unique entries."""
+    M = np.empty(moments[0].shape + (4, 4))
+    for (i, j), m in zip(_UPPER, moments):
+        M[..., i, j] = M[..., j, i] = m
+    return M
+
+
+def _assemble_fe_draws(prods, fplus, fcross, rcond=1e-12, amplitudes=False):
+    """Fe(draw, f) from per-pulsar corrected products, the one 4x4
+    assembly of the host side.  ``prods``: (P, D, 5, F) array of [ss, cc,
+    sc, sr, cr]; ``fplus`` / ``fcross``: (P,) antenna coefficients.
+    Returns (D, F), or with ``amplitudes`` the pair ``(fe (D, F), a (D, F,
+    4))`` with the maximum-likelihood amplitudes ``a = M^-1 N``.
+
+    M is assembled per (draw, frequency) from sums over pulsars and
+    solved as a 4x4 system; near-degenerate skies (e.g. all pulsars
+    clustered: F+/Fx columns collinear) go through the pseudo-inverse —
+    the maximized likelihood is well-defined on the column space."""
+    M = _full_m(_moments(prods, fplus, fcross))
+    sr, cr = prods[:, :, 3], prods[:, :, 4]
+    N = np.stack([_psum(fplus, sr), _psum(fplus, cr),
+                  _psum(fcross, sr), _psum(fcross, cr)], axis=-1)  # (D, F, 4)
     x = _solve4(M, N, rcond)
-    fe = 0.5 * np.einsum("fi,fi->f", N, x)
+    fe = 0.5 * np.einsum("dfi,dfi->df", N, x)
     return (fe, x) if amplitudes else fe
+
+
+def _assemble_fe(prods, fplus, fcross, rcond=1e-12, amplitudes=False):
+    """:func:`_assemble_fe_draws` for one draw: ``prods`` (P, 5, F) ->
+    (F,), or with ``amplitudes`` -> ``(fe (F,), a (F, 4))``."""
+    out = _assemble_fe_draws(prods[:, None], fplus, fcross, rcond, amplitudes)
+    return (out[0][0], out[1][0]) if amplitudes else out[0]
+
+
+def _default_device(device):
+    return device or ("cuda" if torch.cuda.is_available() else "cpu")
 
 
 def _check_assemble(assemble, device, engine):
@@ -221,8 +244,7 @@ def _check_assemble(assemble, device, engine):
     if assemble not in ("host", "device"):
         raise ValueError(
             f"assemble must be 'host' or 'device', got {assemble!r}")
-    if device is None:
-        device = "cuda" if torch.cuda.is_available() else "cpu"
+    device = _default_device(device)
     if assemble == "device":
         dev = engine.device if engine is not None else torch.device(device)
         if dev.type != "cuda":
@@ -233,22 +255,27 @@ def _check_assemble(assemble, device, engine):
     return device
 
 
-def _require_hip_engine(engine):
-    if not engine._use_hip:
-        raise ValueError(
-            "assemble='device' needs an engine on the HIP path "
-            "(force_eager engines have no HIP products)")
+def _obtain_engine(engine, psrs, freqs, Nvecs, Ts, device, freq_chunk=2048,
+                   compress=None):
+    """The caller's engine as it is, or a fresh one on ``device`` (by
+    default the GPU where there is one) precomputed on ``freqs``, with
+    draw compression around ``compress = (rn_sigs, samples)`` if given."""
+    if engine is not None:
+        return engine
+    engine = FpEngine(psrs, Nvecs, Ts, device=_default_device(device))
+    engine.precompute(freqs, freq_chunk=freq_chunk)
+    if compress is not None:
+        engine.compress_around_first_draw(*compress)
+    return engine
 
 
 def _phiinvs_from_sigmas(engine, sigmas):
     """Fixed-noise (m, m) sigmas -> per-pulsar diagonal phi^-1 (the
     ``get_mats_fp`` contract sigma = TNT + diag(phi^-1), as in
     ``FpEngine.sweep``)."""
-    out = []
-    for blk, sg in zip(engine.blocks, sigmas):
-        sg = _t64(sg, engine.device)
-        out.append((torch.diagonal(sg) - torch.diagonal(blk.TNT)).contiguous())
-    return out
+    return [(torch.diagonal(_t64(sg, engine.device))
+             - torch.diagonal(blk.TNT)).contiguous()
+            for blk, sg in zip(engine.blocks, sigmas)]
 
 
 def _antenna_table(pos, sky, device=None):
@@ -262,46 +289,28 @@ def _antenna_table(pos, sky, device=None):
     return torch.as_tensor(ant, dtype=torch.float64).to(device)
 
 
-def _host_max_amplitudes(assemble, prods, coeffs):
-    """Host reference of the sky maximum with amplitudes.  ``assemble``
-    is ``_assemble_fe`` or ``_assemble_fe_draws``, ``coeffs`` the (F+,
-    Fx) pair of every sky point.  Returns ``(femax, argmax, amps)`` of
-    the assembly's output shape (+ (4,) for ``amps``); the solve is
-    repeated with amplitudes only at the sky points that hold a
-    maximum."""
-    grid = np.stack([assemble(prods, fplus, fcross)
-                     for fplus, fcross in coeffs])  # (nsky, ...)
-    femax = np.nanmax(grid, axis=0)
-    argmax = np.nanargmax(grid, axis=0)
-    amps = np.empty(argmax.shape + (4,))
-    for k in np.unique(argmax):
-        _, a = assemble(prods, *coeffs[k], amplitudes=True)
-        sel = argmax == k
-        amps[sel] = a[sel]
-    return femax, argmax, amps
-
-
 _NOT_PD = ("the product block [[ss, sc], [sc, cc]] of (pulsar {p}, draw {d}, "
            "frequency {f}) is not positive definite: it is no covariance to "
            "draw noise-only products from")
 
 
-def _null_factors(prods):
+def _null_factors(prods, xp=np):
     """Cholesky factors ``(l00, l10, l11)``, each (P, D, F), of the
-    per-pulsar blocks ``B_p = [[ss, sc], [sc, cc]]`` of ``prods``
-    (P, D, 5, F).  Raises ``ValueError`` naming the first (pulsar, draw,
+    per-pulsar blocks ``[[ss, sc], [sc, cc]]`` of ``prods`` (P, D, 5, F):
+    numpy arrays, or with ``xp=torch`` tensors beside ``prods`` (one
+    sync).  Raises ``ValueError`` naming the first (pulsar, draw,
     frequency) whose block is not positive definite (``ss <= 0``, a Schur
     complement ``<= 0`` or a non-finite value)."""
     ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
     with np.errstate(all="ignore"):
-        l00 = np.sqrt(ss)
+        l00 = xp.sqrt(ss)
         l10 = sc / l00
         schur = cc - l10 * l10
-        l11 = np.sqrt(schur)
-    ok = (np.isfinite(ss) & np.isfinite(cc) & np.isfinite(sc)
-          & np.isfinite(l10) & np.isfinite(schur) & (ss > 0) & (schur > 0))
-    if not ok.all():
-        p, d, f = (int(i) for i in np.argwhere(~ok)[0])
+        l11 = xp.sqrt(schur)
+    ok = (xp.isfinite(ss) & xp.isfinite(cc) & xp.isfinite(sc)
+          & xp.isfinite(l10) & xp.isfinite(schur) & (ss > 0) & (schur > 0))
+    if not bool(ok.all()):
+        p, d, f = (int(i) for i in xp.argwhere(~ok)[0])
         raise ValueError(_NOT_PD.format(p=p, d=d, f=f))
     return l00, l10, l11
 
@@ -316,6 +325,37 @@ def _null_draws(prods, z):
     return l00[..., None] * z0, l10[..., None] * z0 + l11[..., None] * z1
 
 
+def _ldl4(moments, rcond):
+    """Elementwise LDL^T of the 4x4 ``M`` given by its ten unique entries
+    (the factorisation and pivot rule of the kernels).  Returns ``(ok,
+    (l10, l20, l30, l21, l31, l32, i0, i1, i2, i3))``: ``ok`` where all
+    four pivots pass, the unit-lower entries and the inverse pivots."""
+    m00, m01, m02, m03, m11, m12, m13, m22, m23, m33 = moments
+
+    def pivot_ok(s, mjj):
+        return (s > rcond * mjj) & (s < np.inf)
+
+    d0 = m00
+    ok = pivot_ok(d0, m00)
+    i0 = 1.0 / d0
+    l10, l20, l30 = m01 * i0, m02 * i0, m03 * i0
+    d1 = m11 - l10 * m01
+    ok &= pivot_ok(d1, m11)
+    i1 = 1.0 / d1
+    t21 = m12 - l20 * m01
+    t31 = m13 - l30 * m01
+    l21, l31 = t21 * i1, t31 * i1
+    d2 = m22 - l20 * m02 - l21 * t21
+    ok &= pivot_ok(d2, m22)
+    i2 = 1.0 / d2
+    t32 = m23 - l30 * m02 - l31 * t21
+    l32 = t32 * i2
+    d3 = m33 - l30 * m03 - l31 * t31 - l32 * t32
+    ok &= pivot_ok(d3, m33)
+    i3 = 1.0 / d3
+    return ok, (l10, l20, l30, l21, l31, l32, i0, i1, i2, i3)
+
+
 def _null_max_host(prods, ant, z, rcond=1e-12):
     """Host reference of ``ops.fe_null_skymax``: the sky maximum of Fe for
     ``R`` noise-only realisations per (draw, frequency) column.
@@ -324,10 +364,10 @@ def _null_max_host(prods, ant, z, rcond=1e-12):
     (nsky, P, 2), ``z`` (D, F, P, 2, R).  Returns ``(femax (R, D, F),
     argmax (R, D, F) int64)``, the lowest sky index on ties.
 
-    Per sky point M is factored ONCE (the LDL^T and pivot rule of the
-    kernels, elementwise over the columns) and all R realisations go
-    through the forward solve; the columns whose M fails a pivot take the
-    pseudo-inverse, as in :func:`_assemble_fe_draws`.  Every step is
+    Per sky point M (the moments of :func:`_assemble_fe_draws`) is
+    factored ONCE, elementwise over the columns, and all R realisations
+    go through the forward solve; the columns whose M fails a pivot take
+    the pseudo-inverse, as in :func:`_assemble_fe_draws`.  Every step is
     elementwise in R: a realisation's value does not depend on how many
     others are computed with it."""
     prods = np.asarray(prods, dtype=np.float64)
@@ -339,46 +379,16 @@ def _null_max_host(prods, ant, z, rcond=1e-12):
                          f" got {z.shape}")
     R = z.shape[4]
     ns, nc = _null_draws(prods, z)
-    ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
     femax = np.full((D, F, R), -np.inf)
     argmax = np.full((D, F, R), -1, dtype=np.int64)
-
-    def w(coeff, q):  # (P,) x (P, D, F[, R]) -> (D, F[, R])
-        return np.einsum("p,p...->...", coeff, q)
-
     for k in range(ant.shape[0]):
         fplus, fcross = ant[k, :, 0], ant[k, :, 1]
-        fp2, fx2, fpx = fplus**2, fcross**2, fplus * fcross
-        m00, m01, m11 = w(fp2, ss), w(fp2, sc), w(fp2, cc)
-        m02, m03, m13 = w(fpx, ss), w(fpx, sc), w(fpx, cc)
-        m22, m23, m33 = w(fx2, ss), w(fx2, sc), w(fx2, cc)
-        m12 = m03
-        N = [w(fplus, ns), w(fplus, nc), w(fcross, ns), w(fcross, nc)]
-
-        def pivot_ok(s, mjj):
-            return (s > rcond * mjj) & (s < np.inf)
-
+        moments = _moments(prods, fplus, fcross)
+        N = [_psum(fplus, ns), _psum(fplus, nc),
+             _psum(fcross, ns), _psum(fcross, nc)]
         with np.errstate(all="ignore"):
-            d0 = m00
-            ok = pivot_ok(d0, m00)
-            i0 = 1.0 / d0
-            l10, l20, l30 = m01 * i0, m02 * i0, m03 * i0
-            d1 = m11 - l10 * m01
-            ok &= pivot_ok(d1, m11)
-            i1 = 1.0 / d1
-            t21 = m12 - l20 * m01
-            t31 = m13 - l30 * m01
-            l21, l31 = t21 * i1, t31 * i1
-            d2 = m22 - l20 * m02 - l21 * t21
-            ok &= pivot_ok(d2, m22)
-            i2 = 1.0 / d2
-            t32 = m23 - l30 * m02 - l31 * t21
-            l32 = t32 * i2
-            d3 = m33 - l30 * m03 - l31 * t31 - l32 * t32
-            ok &= pivot_ok(d3, m33)
-            i3 = 1.0 / d3
-            e = [x[..., None] for x in
-                 (l10, l20, l30, l21, l31, l32, i0, i1, i2, i3)]
+            ok, fac = _ldl4(moments, rcond)
+            e = [x[..., None] for x in fac]
             z0 = N[0]
             z1 = N[1] - e[0] * z0
             z2 = N[2] - e[1] * z0 - e[3] * z1
@@ -386,17 +396,7 @@ def _null_max_host(prods, ant, z, rcond=1e-12):
             fe = 0.5 * (z0 * z0 * e[6] + z1 * z1 * e[7] + z2 * z2 * e[8]
                         + z3 * z3 * e[9])  # (D, F, R)
         if not ok.all():
-            M = np.empty((D, F, 4, 4))
-            M[..., 0, 0] = m00
-            M[..., 0, 1] = M[..., 1, 0] = m01
-            M[..., 0, 2] = M[..., 2, 0] = m02
-            M[..., 0, 3] = M[..., 3, 0] = m03
-            M[..., 1, 1] = m11
-            M[..., 1, 2] = M[..., 2, 1] = m12
-            M[..., 1, 3] = M[..., 3, 1] = m13
-            M[..., 2, 2] = m22
-            M[..., 2, 3] = M[..., 3, 2] = m23
-            M[..., 3, 3] = m33
+            M = _full_m(moments)
             for d, f in np.argwhere(~ok):
                 Mi = np.linalg.pinv(M[d, f], rcond=rcond)
                 acc = 0.0
@@ -410,44 +410,98 @@ def _null_max_host(prods, ant, z, rcond=1e-12):
     return np.moveaxis(femax, 2, 0), np.moveaxis(argmax, 2, 0)
 
 
-def _null_chunks(prods, ant, nreal, seed, real_chunk, z, device, hip,
-                 gen=None):
-    """(nreal, D, F) null sky maxima of one product set, ``real_chunk``
-    realisations at a time.  ``prods`` / ``ant``: device tensors (``hip``)
-    or numpy arrays.  ``z`` (D, F, P, 2, nreal) bypasses the generator;
-    otherwise each chunk is ONE ``torch.randn`` call on ``device`` from
-    ``gen`` (a fresh generator seeded with ``seed`` when none is
-    passed)."""
-    P, D, F = prods.shape[0], prods.shape[1], prods.shape[3]
-    nreal, real_chunk = int(nreal), int(real_chunk)
-    if nreal < 1 or real_chunk < 1:
-        raise ValueError("nreal and real_chunk must be at least 1")
-    if z is not None:
-        if tuple(z.shape) != (D, F, P, 2, nreal):
-            raise ValueError(
-                f"z must be (D, F, P, 2, nreal) = ({D}, {F}, {P}, 2, "
-                f"{nreal}), got {tuple(z.shape)}")
-        z = torch.as_tensor(z, dtype=torch.float64)
-    elif gen is None:
-        gen = torch.Generator(device=device)
-        gen.manual_seed(int(seed))
-    out = np.empty((nreal, D, F))
-    for lo in range(0, nreal, real_chunk):
-        hi = min(lo + real_chunk, nreal)
-        if z is None:
-            zc = torch.randn((D, F, P, 2, hi - lo), generator=gen,
-                             dtype=torch.float64, device=device)
-        else:
-            zc = z[..., lo:hi]
-        if hip:
-            from fastfp_amd import ops
+class _Sky:
+    """The sky layer under :class:`FastFe` and :class:`NMFe`: the antenna
+    table of ``sky`` and the four sky operations on a product set
+    (P, D, 5, F).  With ``hip`` (default: ``engine`` is on the HIP path)
+    table and products are device tensors and the operations the
+    ``ops.fe_*`` kernels, otherwise numpy arrays and the host assembly.
+    Only this class makes that choice; every result is a numpy array."""
 
-            fm, _, _ = ops.fe_null_skymax(
-                prods, ant, zc.to(prods.device).contiguous())
-            out[lo:hi] = fm.cpu().numpy()
-        else:
-            out[lo:hi] = _null_max_host(prods, ant, zc.cpu().numpy())[0]
-    return out
+    def __init__(self, pos, sky, engine, hip=None):
+        self.hip = engine._use_hip if hip is None else hip
+        if self.hip and not engine._use_hip:
+            raise ValueError(
+                "assemble='device' needs an engine on the HIP path "
+                "(force_eager engines have no HIP products)")
+        self.device = engine.device
+        self.ant = _antenna_table(pos, sky, self.device if self.hip else None)
+
+    def _grid(self, prods):
+        """The host assembly stacked over the sky: (nsky, D, F)."""
+        return np.stack([_assemble_fe_draws(prods, a[:, 0], a[:, 1])
+                         for a in self.ant])
+
+    def map(self, prods):
+        """Fe over (draw, sky, frequency): (D, nsky, F)."""
+        if self.hip:
+            return ops.fe_assemble(prods, self.ant).cpu().numpy()
+        return np.moveaxis(self._grid(prods), 0, 1)
+
+    def max(self, prods, amplitudes=False):
+        """Fe maximised over the sky: ``(femax (D, F), argmax (D, F) int64)``,
+        with ``amplitudes`` also ``amps (D, F, 4)`` at the maximum: on the
+        host re-solved only at the sky rows that hold a maximum."""
+        if self.hip:
+            femax, argmax, _ = ops.fe_skymax(prods, self.ant)
+            out = (femax.cpu().numpy(), argmax.cpu().numpy().astype(np.int64))
+            if amplitudes:
+                amps, _, _ = ops.fe_amplitudes(prods, self.ant, argmax)
+                out += (amps.cpu().numpy(),)
+            return out
+        grid = self._grid(prods)
+        argmax = np.nanargmax(grid, axis=0)
+        out = (np.nanmax(grid, axis=0), argmax)
+        if amplitudes:
+            amps = np.empty(argmax.shape + (4,))
+            for k in np.unique(argmax):
+                sel = argmax == k
+                amps[sel] = self.amplitudes(prods, k)[1][sel]
+            out += (amps,)
+        return out
+
+    def amplitudes(self, prods, k=0):
+        """``(fe (D, F), amps (D, F, 4))`` at sky row ``k``."""
+        if self.hip:
+            idx = torch.full((prods.shape[1], prods.shape[3]), int(k),
+                             dtype=torch.int32, device=prods.device)
+            amps, fe, _ = ops.fe_amplitudes(prods, self.ant, idx)
+            return fe.cpu().numpy(), amps.cpu().numpy()
+        return _assemble_fe_draws(prods, self.ant[k, :, 0], self.ant[k, :, 1],
+                                  amplitudes=True)
+
+    def null_max(self, prods, nreal, seed, real_chunk, z=None, gen=None):
+        """(nreal, D, F) null sky maxima of one product set, ``real_chunk``
+        realisations at a time.  ``z`` (D, F, P, 2, nreal) bypasses the
+        generator; otherwise each chunk is ONE ``torch.randn`` call on the
+        engine's device from ``gen`` (by default a fresh one of ``seed``)."""
+        P, D, F = prods.shape[0], prods.shape[1], prods.shape[3]
+        nreal, real_chunk = int(nreal), int(real_chunk)
+        if nreal < 1 or real_chunk < 1:
+            raise ValueError("nreal and real_chunk must be at least 1")
+        if z is not None:
+            if tuple(z.shape) != (D, F, P, 2, nreal):
+                raise ValueError(
+                    f"z must be (D, F, P, 2, nreal) = ({D}, {F}, {P}, 2, "
+                    f"{nreal}), got {tuple(z.shape)}")
+            z = torch.as_tensor(z, dtype=torch.float64)
+        elif gen is None:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(int(seed))
+        out = np.empty((nreal, D, F))
+        for lo in range(0, nreal, real_chunk):
+            hi = min(lo + real_chunk, nreal)
+            zc = z[..., lo:hi] if z is not None else torch.randn(
+                (D, F, P, 2, hi - lo), generator=gen, dtype=torch.float64,
+                device=self.device)
+            if self.hip:
+                fm, _, _ = ops.fe_null_skymax(
+                    prods, self.ant, zc.to(prods.device).contiguous())
+                out[lo:hi] = fm.cpu().numpy()
+            else:
+                out[lo:hi] = _null_max_host(prods, self.ant,
+                                            zc.cpu().numpy())[0]
+        return out
 
 
 def false_alarm_probability(femax, null):
@@ -506,18 +560,28 @@ class FastFe:
     # ------------------------------------------------------------------
     # production path: whole (sky x freq) grid from one engine pass
     # ------------------------------------------------------------------
-    def sweep(
-        self,
-        freqs,
-        sky,
-        Nvecs,
-        Ts,
-        sigmas,
-        device: str = None,
-        freq_chunk: int = 2048,
-        engine: FpEngine = None,
-        assemble: str = "host",
-    ) -> np.ndarray:
+    @staticmethod
+    def _products(engine, sigmas, hip):
+        """The fixed-noise products as the one-draw set (P, 1, 5, F): a
+        device tensor from the HIP solve (``hip``), otherwise a numpy
+        array from the torch path on the dense ``sigmas``."""
+        if hip:
+            return engine.sweep_products_hip(
+                _phiinvs_from_sigmas(engine, sigmas))[:, None].contiguous()
+        return engine.sweep_products(sigmas=sigmas).cpu().numpy()[:, None]
+
+    def _setup(self, freqs, sky, Nvecs, Ts, sigmas, device, engine,
+               freq_chunk=2048, hip=None):
+        """``(layer, prods)``: the sky layer of ``sky`` on the caller's
+        engine (or one built here) and the products it takes."""
+        engine = _obtain_engine(engine, self.psrs, freqs, Nvecs, Ts, device,
+                                freq_chunk)
+        layer = _Sky(self.pos, sky, engine, hip)
+        return layer, self._products(engine, sigmas, layer.hip)
+
+    def sweep(self, freqs, sky, Nvecs, Ts, sigmas, device: str = None,
+              freq_chunk: int = 2048, engine: FpEngine = None,
+              assemble: str = "host") -> np.ndarray:
         """Fe over ``freqs`` x ``sky`` (list of (gwtheta, gwphi)).
 
         Returns (nsky, F).  The per-pulsar corrected products are
@@ -531,45 +595,20 @@ class FastFe:
         assembly.
         """
         device = _check_assemble(assemble, device, engine)
-        if engine is None:
-            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
-            engine.precompute(freqs, freq_chunk=freq_chunk)
-        if assemble == "device":
-            from fastfp_amd import ops
+        layer, prods = self._setup(freqs, sky, Nvecs, Ts, sigmas, device,
+                                   engine, freq_chunk, assemble == "device")
+        return layer.map(prods)[0]
 
-            _require_hip_engine(engine)
-            prods = engine.sweep_products_hip(
-                _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
-            fe = ops.fe_assemble(prods[:, None].contiguous(),
-                                 _antenna_table(self.pos, sky, engine.device))
-            return fe[0].cpu().numpy()
-        prods = engine.sweep_products(sigmas=sigmas)  # (P, 5, F) tensor
-        prods = prods.cpu().numpy()
-        out = np.empty((len(sky), prods.shape[2]))
-        for k, (gwtheta, gwphi) in enumerate(sky):
-            fplus, fcross = gw_antenna_pattern(self.pos, gwtheta, gwphi)
-            out[k] = _assemble_fe(prods, fplus, fcross)
-        return out
-
-    def sweep_max(
-        self,
-        freqs,
-        sky,
-        Nvecs,
-        Ts,
-        sigmas,
-        device: str = None,
-        engine: FpEngine = None,
-        amplitudes: bool = False,
-    ):
+    def sweep_max(self, freqs, sky, Nvecs, Ts, sigmas, device: str = None,
+                  engine: FpEngine = None, amplitudes: bool = False):
         """Fe maximised over ``sky`` per frequency.
 
         Returns ``(femax (F,), argmax (F,))``; ``argmax`` indexes into
         ``sky``.  On a HIP engine the products come from the HIP solve
         and the ``fe_skymax`` kernel keeps the running maximum, so only
         (F,)-sized results leave the device; on a CPU engine this is the
-        host assembly followed by ``np.nanmax`` / ``np.nanargmax`` (the
-        reference implementation).
+        host assembly followed by the NaN-ignoring maximum over the sky
+        (the reference implementation).
 
         ``amplitudes``: return ``(femax, argmax, amps (F, 4))`` with the
         maximum-likelihood amplitudes ``M^-1 N`` at the maximum
@@ -577,104 +616,27 @@ class FastFe:
         HIP engine the ``fe_amplitudes`` kernel reads the same device
         products at ``argmax``; on a CPU engine it is the host solve.
         """
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
-        if engine is None:
-            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
-            engine.precompute(freqs)
-        if engine._use_hip:
-            from fastfp_amd import ops
+        layer, prods = self._setup(freqs, sky, Nvecs, Ts, sigmas, device,
+                                   engine)
+        return tuple(x[0] for x in layer.max(prods, amplitudes))
 
-            prods = engine.sweep_products_hip(
-                _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
-            prods = prods[:, None].contiguous()
-            ant_d = _antenna_table(self.pos, sky, engine.device)
-            femax, argmax, _ = ops.fe_skymax(prods, ant_d)
-            out = (femax[0].cpu().numpy(),
-                   argmax[0].cpu().numpy().astype(np.int64))
-            if amplitudes:
-                amps, _, _ = ops.fe_amplitudes(prods, ant_d, argmax)
-                out += (amps[0].cpu().numpy(),)
-            return out
-        if amplitudes:
-            # the assembly of ``sweep``, call for call
-            prods = engine.sweep_products(sigmas=sigmas).cpu().numpy()
-            return _host_max_amplitudes(
-                _assemble_fe, prods,
-                [gw_antenna_pattern(self.pos, th, ph) for th, ph in sky])
-        grid = self.sweep(freqs, sky, Nvecs, Ts, sigmas, engine=engine)
-        return np.nanmax(grid, axis=0), np.nanargmax(grid, axis=0)
-
-    def amplitudes(
-        self,
-        freqs,
-        gwtheta,
-        gwphi,
-        Nvecs,
-        Ts,
-        sigmas,
-        device: str = None,
-        engine: FpEngine = None,
-    ):
+    def amplitudes(self, freqs, gwtheta, gwphi, Nvecs, Ts, sigmas,
+                   device: str = None, engine: FpEngine = None):
         """Targeted search at one sky position: ``(fe (F,), amps (F,
         4))``, the statistic and the maximum-likelihood amplitudes
         ``M^-1 N`` per frequency.  HIP engine: products from the HIP
         solve, ``fe_amplitudes`` kernel; CPU engine: the host solve."""
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
-        if engine is None:
-            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
-            engine.precompute(freqs)
-        sky = [(float(gwtheta), float(gwphi))]
-        if engine._use_hip:
-            from fastfp_amd import ops
-
-            prods = engine.sweep_products_hip(
-                _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
-            prods = prods[:, None].contiguous()
-            idx = torch.zeros((1, prods.shape[3]), dtype=torch.int32,
-                              device=prods.device)
-            amps, fe, _ = ops.fe_amplitudes(
-                prods, _antenna_table(self.pos, sky, engine.device), idx)
-            return fe[0].cpu().numpy(), amps[0].cpu().numpy()
-        prods = engine.sweep_products(sigmas=sigmas).cpu().numpy()
-        fplus, fcross = gw_antenna_pattern(self.pos, *sky[0])
-        return _assemble_fe(prods, fplus, fcross, amplitudes=True)
+        layer, prods = self._setup(freqs, [(float(gwtheta), float(gwphi))],
+                                   Nvecs, Ts, sigmas, device, engine)
+        fe, amps = layer.amplitudes(prods)
+        return fe[0], amps[0]
 
     # ------------------------------------------------------------------
     # significance of the sky maximum
     # ------------------------------------------------------------------
-    def _null_inputs(self, freqs, sky, Nvecs, Ts, sigmas, device, engine):
-        """``(engine, prods (P, 1, 5, F), ant (nsky, P, 2))``: device
-        tensors from the HIP solve on a HIP engine, numpy arrays
-        otherwise."""
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
-        if engine is None:
-            engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
-            engine.precompute(freqs)
-        if engine._use_hip:
-            prods = engine.sweep_products_hip(
-                _phiinvs_from_sigmas(engine, sigmas))  # (P, 5, F)
-            return (engine, prods[:, None].contiguous(),
-                    _antenna_table(self.pos, sky, engine.device))
-        prods = engine.sweep_products(sigmas=sigmas).cpu().numpy()
-        return engine, prods[:, None], _antenna_table(self.pos, sky)
-
-    def null_max(
-        self,
-        freqs,
-        sky,
-        Nvecs,
-        Ts,
-        sigmas,
-        nreal: int,
-        seed: int = 0,
-        device: str = None,
-        engine: FpEngine = None,
-        real_chunk: int = 256,
-        z=None,
-    ) -> np.ndarray:
+    def null_max(self, freqs, sky, Nvecs, Ts, sigmas, nreal: int,
+                 seed: int = 0, device: str = None, engine: FpEngine = None,
+                 real_chunk: int = 256, z=None) -> np.ndarray:
         """The sky-maximised Fe of ``nreal`` noise-only realisations per
         frequency: ``(nreal, F)``, the Monte-Carlo null distribution of
         what :meth:`sweep_max` returns.
@@ -702,25 +664,13 @@ class FastFe:
         out of scope; so is a signal-present mean for detection-
         probability curves.
         """
-        engine, prods, ant = self._null_inputs(freqs, sky, Nvecs, Ts, sigmas,
-                                               device, engine)
-        return _null_chunks(prods, ant, nreal, seed, real_chunk, z,
-                            engine.device, engine._use_hip)[:, 0, :]
+        layer, prods = self._setup(freqs, sky, Nvecs, Ts, sigmas, device,
+                                   engine)
+        return layer.null_max(prods, nreal, seed, real_chunk, z)[:, 0, :]
 
-    def false_alarm(
-        self,
-        freqs,
-        sky,
-        Nvecs,
-        Ts,
-        sigmas,
-        nreal: int,
-        seed: int = 0,
-        device: str = None,
-        engine: FpEngine = None,
-        real_chunk: int = 256,
-        z=None,
-    ):
+    def false_alarm(self, freqs, sky, Nvecs, Ts, sigmas, nreal: int,
+                    seed: int = 0, device: str = None, engine: FpEngine = None,
+                    real_chunk: int = 256, z=None):
         """The observed sky maximum and its false-alarm probability:
         ``(femax (F,), argmax (F,), pfa (F,))`` with ``femax, argmax`` as
         :meth:`sweep_max` returns them and
@@ -732,22 +682,10 @@ class FastFe:
         single-frequency probability, no trials factor over frequency).
         The products and the antenna table are computed once and serve
         both passes."""
-        engine, prods, ant = self._null_inputs(freqs, sky, Nvecs, Ts, sigmas,
-                                               device, engine)
-        if engine._use_hip:
-            from fastfp_amd import ops
-
-            fm, am, _ = ops.fe_skymax(prods, ant)
-            femax = fm[0].cpu().numpy()
-            argmax = am[0].cpu().numpy().astype(np.int64)
-        else:
-            # the assembly of ``sweep_max`` on a CPU engine, call for call
-            grid = np.stack([_assemble_fe(prods[:, 0], ant[k, :, 0],
-                                          ant[k, :, 1])
-                             for k in range(ant.shape[0])])
-            femax, argmax = np.nanmax(grid, axis=0), np.nanargmax(grid, axis=0)
-        null = _null_chunks(prods, ant, nreal, seed, real_chunk, z,
-                            engine.device, engine._use_hip)[:, 0, :]
+        layer, prods = self._setup(freqs, sky, Nvecs, Ts, sigmas, device,
+                                   engine)
+        femax, argmax = (x[0] for x in layer.max(prods))
+        null = layer.null_max(prods, nreal, seed, real_chunk, z)[:, 0, :]
         return femax, argmax, false_alarm_probability(femax, null)
 
 
@@ -758,36 +696,6 @@ def compute_Fe(psrs, pta, noise, freqs, sky, device=None) -> np.ndarray:
     Nvecs, Ts, sigmas = get_mats_fp(pta, noise)
     return FastFe(psrs, pta).sweep(freqs, sky, Nvecs, Ts, sigmas,
                                    device=device)
-
-
-def _assemble_fe_draws(prods, fplus, fcross, rcond=1e-12, amplitudes=False):
-    """Draw-batched Fe assembly: ``prods`` (P, D, 5, F) -> (D, F), or
-    with ``amplitudes`` -> ``(fe (D, F), a (D, F, 4))``."""
-    ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
-    sr, cr = prods[:, :, 3], prods[:, :, 4]
-    fp2, fx2, fpx = fplus**2, fcross**2, fplus * fcross
-
-    def w(coeff, q):  # (P,) x (P, D, F) -> (D, F)
-        return np.einsum("p,pdf->df", coeff, q)
-
-    D, F = prods.shape[1], prods.shape[3]
-    M = np.empty((D, F, 4, 4))
-    M[..., 0, 0] = w(fp2, ss)
-    M[..., 0, 1] = M[..., 1, 0] = w(fp2, sc)
-    M[..., 0, 2] = M[..., 2, 0] = w(fpx, ss)
-    M[..., 0, 3] = M[..., 3, 0] = w(fpx, sc)
-    M[..., 1, 1] = w(fp2, cc)
-    M[..., 1, 2] = M[..., 2, 1] = w(fpx, sc)
-    M[..., 1, 3] = M[..., 3, 1] = w(fpx, cc)
-    M[..., 2, 2] = w(fx2, ss)
-    M[..., 2, 3] = M[..., 3, 2] = w(fx2, sc)
-    M[..., 3, 3] = w(fx2, cc)
-    N = np.stack(
-        [w(fplus, sr), w(fplus, cr), w(fcross, sr), w(fcross, cr)], axis=-1
-    )  # (D, F, 4)
-    x = _solve4(M, N, rcond)
-    fe = 0.5 * np.einsum("dfi,dfi->df", N, x)
-    return (fe, x) if amplitudes else fe
 
 
 class NMFe:
@@ -804,17 +712,14 @@ class NMFe:
         self.rn_sigs = rn_sigs
         self.fe = FastFe(psrs)  # validates .pos, holds antenna inputs
 
-    def _engine(self, engine, freqs, samples, Nvecs, Ts, device, compress,
-                freq_chunk=2048):
-        """The caller's engine, or a fresh one on ``device`` — with draw
-        compression enabled around the first draw when ``compress``."""
-        if engine is not None:
-            return engine
-        engine = FpEngine(self.psrs, Nvecs, Ts, device=device)
-        engine.precompute(freqs, freq_chunk=freq_chunk)
-        if compress:
-            engine.compress_around_first_draw(self.rn_sigs, samples)
-        return engine
+    def _layer(self, freqs, sky, samples, Nvecs, Ts, device, engine, compress,
+               freq_chunk=2048, hip=None):
+        """``(engine, layer)``: the caller's engine, or one built here (with
+        draw compression when ``compress``), and the sky layer on it."""
+        engine = _obtain_engine(
+            engine, self.psrs, freqs, Nvecs, Ts, device, freq_chunk,
+            (self.rn_sigs, samples) if compress else None)
+        return engine, _Sky(self.fe.pos, sky, engine, hip)
 
     @staticmethod
     def _products(engine, chunk, compress: bool, hip: bool):
@@ -836,20 +741,21 @@ class NMFe:
         return engine.margin_split(
             chunk, lambda rows: run(rows, compressed=True), run, dim=1)
 
-    def sweep(
-        self,
-        freqs,
-        sky,
-        samples: dict,
-        Nvecs,
-        Ts,
-        device: str = None,
-        draw_chunk: int = 128,
-        freq_chunk: int = 2048,
-        engine: FpEngine = None,
-        assemble: str = "host",
-        compress: bool = False,
-    ) -> np.ndarray:
+    def _draw_chunks(self, engine, samples, draw_chunk, compress, hip):
+        """The products of ``samples``, ``draw_chunk`` draws at a time and
+        in draw order, as the sky layer takes them: (P, Dc, 5, F) device
+        tensors (``hip``) or numpy arrays."""
+        phiinvs = batch_phiinv(self.rn_sigs, samples)
+        phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
+        for lo in range(0, phiinvs[0].shape[0], draw_chunk):
+            chunk = [p[lo:lo + draw_chunk] for p in phiinvs]
+            prods = self._products(engine, chunk, compress, hip)
+            yield prods if hip else prods.cpu().numpy()
+
+    def sweep(self, freqs, sky, samples: dict, Nvecs, Ts, device: str = None,
+              draw_chunk: int = 128, freq_chunk: int = 2048,
+              engine: FpEngine = None, assemble: str = "host",
+              compress: bool = False) -> np.ndarray:
         """Fe over (draws x sky x freqs).  ``samples``: parameter-name
         -> (D,) arrays (the ``map_params`` format).  Returns
         (D, nsky, F).
@@ -863,52 +769,18 @@ class NMFe:
         per-draw systems (``NMFp.sweep``'s ``compress``), draw by draw
         where the compression margin allows.  An engine built here gets
         compression enabled; a caller's engine is used as it is."""
-        from fastfp_amd.noise import batch_phiinv
-
         device = _check_assemble(assemble, device, engine)
-        engine = self._engine(engine, freqs, samples, Nvecs, Ts, device,
-                              compress, freq_chunk)
-        phiinvs = batch_phiinv(self.rn_sigs, samples)
-        phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
-        D = phiinvs[0].shape[0]
-        F = engine.freqs.shape[0]
-        if assemble == "device":
-            from fastfp_amd import ops
+        engine, layer = self._layer(freqs, sky, samples, Nvecs, Ts, device,
+                                    engine, compress, freq_chunk,
+                                    assemble == "device")
+        return np.concatenate([
+            layer.map(prods) for prods in self._draw_chunks(
+                engine, samples, draw_chunk, compress, layer.hip)])
 
-            _require_hip_engine(engine)
-            ant_d = _antenna_table(self.fe.pos, sky, engine.device)
-            out = np.empty((D, len(sky), F))
-            for lo in range(0, D, draw_chunk):
-                hi = min(lo + draw_chunk, D)
-                prods = self._products(
-                    engine, [p[lo:hi] for p in phiinvs], compress,
-                    hip=True)  # (P, Dc, 5, F)
-                out[lo:hi] = ops.fe_assemble(prods, ant_d).cpu().numpy()
-            return out
-        ant = [gw_antenna_pattern(self.fe.pos, th, ph) for th, ph in sky]
-        out = np.empty((D, len(sky), F))
-        for lo in range(0, D, draw_chunk):
-            hi = min(lo + draw_chunk, D)
-            prods = self._products(
-                engine, [p[lo:hi] for p in phiinvs], compress, hip=False
-            ).cpu().numpy()  # (P, Dc, 5, F)
-            for k, (fplus, fcross) in enumerate(ant):
-                out[lo:hi, k, :] = _assemble_fe_draws(prods, fplus, fcross)
-        return out
-
-    def sweep_max(
-        self,
-        freqs,
-        sky,
-        samples: dict,
-        Nvecs,
-        Ts,
-        device: str = None,
-        draw_chunk: int = 128,
-        engine: FpEngine = None,
-        compress: bool = False,
-        amplitudes: bool = False,
-    ):
+    def sweep_max(self, freqs, sky, samples: dict, Nvecs, Ts,
+                  device: str = None, draw_chunk: int = 128,
+                  engine: FpEngine = None, compress: bool = False,
+                  amplitudes: bool = False):
         """Fe maximised over ``sky`` for every (draw, frequency).
 
         Returns ``(femax (D, F), argmax (D, F))``; ``argmax`` indexes
@@ -916,80 +788,23 @@ class NMFe:
         engine each draw chunk goes products (HIP solve) ->
         ``fe_skymax`` kernel and only (Dc, F)-sized results leave the
         device; on a CPU engine each chunk is assembled on the host and
-        reduced with ``np.nanmax`` / ``np.nanargmax`` (the reference
+        reduced with the NaN-ignoring maximum over the sky (the reference
         implementation).  ``compress``: as in :meth:`sweep`.
 
         ``amplitudes``: return ``(femax, argmax, amps (D, F, 4))`` with
         the maximum-likelihood amplitudes at each maximum, as in
         :meth:`FastFe.sweep_max`.
         """
-        from fastfp_amd.noise import batch_phiinv
+        engine, layer = self._layer(freqs, sky, samples, Nvecs, Ts, device,
+                                    engine, compress)
+        parts = [layer.max(prods, amplitudes) for prods in self._draw_chunks(
+            engine, samples, draw_chunk, compress, layer.hip)]
+        return tuple(np.concatenate(col) for col in zip(*parts))
 
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
-        engine = self._engine(engine, freqs, samples, Nvecs, Ts, device,
-                              compress)
-        phiinvs = batch_phiinv(self.rn_sigs, samples)
-        phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
-        D = phiinvs[0].shape[0]
-        F = engine.freqs.shape[0]
-        femax = np.empty((D, F))
-        argmax = np.empty((D, F), dtype=np.int64)
-        amps = np.empty((D, F, 4)) if amplitudes else None
-        if engine._use_hip:
-            from fastfp_amd import ops
-
-            ant_d = _antenna_table(self.fe.pos, sky, engine.device)
-        else:
-            ant = _antenna_table(self.fe.pos, sky)
-        for lo in range(0, D, draw_chunk):
-            hi = min(lo + draw_chunk, D)
-            chunk = [p[lo:hi] for p in phiinvs]
-            if engine._use_hip:
-                prods = self._products(engine, chunk, compress,
-                                       hip=True)  # (P, Dc, 5, F)
-                fm, am, _ = ops.fe_skymax(prods, ant_d)
-                femax[lo:hi] = fm.cpu().numpy()
-                argmax[lo:hi] = am.cpu().numpy()
-                if amplitudes:
-                    amps[lo:hi] = ops.fe_amplitudes(
-                        prods, ant_d, am)[0].cpu().numpy()
-            elif amplitudes:
-                prods = self._products(engine, chunk, compress,
-                                       hip=False).cpu().numpy()
-                femax[lo:hi], argmax[lo:hi], amps[lo:hi] = \
-                    _host_max_amplitudes(
-                        _assemble_fe_draws, prods,
-                        [(ant[k, :, 0], ant[k, :, 1])
-                         for k in range(len(sky))])
-            else:
-                prods = self._products(engine, chunk, compress,
-                                       hip=False).cpu().numpy()
-                cube = np.stack([
-                    _assemble_fe_draws(prods, ant[k, :, 0], ant[k, :, 1])
-                    for k in range(len(sky))
-                ])  # (nsky, Dc, F)
-                femax[lo:hi] = np.nanmax(cube, axis=0)
-                argmax[lo:hi] = np.nanargmax(cube, axis=0)
-        if amplitudes:
-            return femax, argmax, amps
-        return femax, argmax
-
-    def null_max(
-        self,
-        freqs,
-        sky,
-        samples: dict,
-        Nvecs,
-        Ts,
-        nreal: int,
-        seed: int = 0,
-        draw_chunk: int = 8,
-        real_chunk: int = 128,
-        engine: FpEngine = None,
-        compress: bool = False,
-        device: str = None,
-    ) -> np.ndarray:
+    def null_max(self, freqs, sky, samples: dict, Nvecs, Ts, nreal: int,
+                 seed: int = 0, draw_chunk: int = 8, real_chunk: int = 128,
+                 engine: FpEngine = None, compress: bool = False,
+                 device: str = None) -> np.ndarray:
         """:meth:`FastFe.null_max` over noise draws: ``(nreal, D, F)``,
         the sky-maximised Fe of ``nreal`` noise-only realisations for
         every (draw, frequency), each draw's realisations drawn from that
@@ -1003,27 +818,11 @@ class NMFe:
         each) and ``draw_chunk * F * P * 2 * real_chunk`` normals, which
         is what the two chunk sizes bound.  Scope as in
         :meth:`FastFe.null_max`."""
-        from fastfp_amd.noise import batch_phiinv
-
-        if device is None:
-            device = "cuda" if torch.cuda.is_available() else "cpu"
-        engine = self._engine(engine, freqs, samples, Nvecs, Ts, device,
-                              compress)
-        phiinvs = batch_phiinv(self.rn_sigs, samples)
-        phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
-        D = phiinvs[0].shape[0]
-        F = engine.freqs.shape[0]
-        hip = engine._use_hip
-        ant = _antenna_table(self.fe.pos, sky, engine.device if hip else None)
+        engine, layer = self._layer(freqs, sky, samples, Nvecs, Ts, device,
+                                    engine, compress)
         gen = torch.Generator(device=engine.device)
         gen.manual_seed(int(seed))
-        out = np.empty((int(nreal), D, F))
-        for lo in range(0, D, draw_chunk):
-            hi = min(lo + draw_chunk, D)
-            prods = self._products(engine, [p[lo:hi] for p in phiinvs],
-                                   compress, hip=hip)  # (P, Dc, 5, F)
-            if not hip:
-                prods = prods.cpu().numpy()
-            out[:, lo:hi] = _null_chunks(prods, ant, nreal, seed, real_chunk,
-                                         None, engine.device, hip, gen=gen)
-        return out
+        return np.concatenate([
+            layer.null_max(prods, nreal, seed, real_chunk, gen=gen)
+            for prods in self._draw_chunks(engine, samples, draw_chunk,
+                                           compress, layer.hip)], axis=1)

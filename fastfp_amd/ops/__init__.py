@@ -265,6 +265,17 @@ def _fe_ext():
     return ext
 
 
+def _host_columns(prods, d_idx, f_idx, z=None):
+    """The (d, f) columns ``d_idx, f_idx`` of the device product set
+    ``prods`` (P, D, 5, F) as a host product set (P, ncols, 5, 1), for the
+    host assembly of ``festat``; with ``z`` (D, F, P, 2, R) also its
+    columns as (ncols, 1, P, 2, R)."""
+    sub = prods[:, d_idx, :, f_idx].permute(1, 0, 2).unsqueeze(-1)
+    if z is None:
+        return sub.cpu().numpy()
+    return sub.cpu().numpy(), z[d_idx, f_idx].unsqueeze(1).cpu().numpy()
+
+
 def fe_assemble(prods, ant, repair: bool = True):
     """Fe over (draw, sky, frequency) on the device.
 
@@ -320,9 +331,7 @@ def fe_skymax(prods, ant, repair: bool = True):
         from fastfp_amd.festat import _assemble_fe_draws
 
         d_idx, f_idx = torch.nonzero(bad, as_tuple=True)
-        # the bad columns as a (P, ncols, 5, 1) product set
-        sub = prods[:, d_idx, :, f_idx]  # (ncols, P, 5)
-        sub_h = sub.permute(1, 0, 2).unsqueeze(-1).cpu().numpy()
+        sub_h = _host_columns(prods, d_idx, f_idx)
         ant_h = ant.cpu().numpy()
         vals = np.stack([
             _assemble_fe_draws(sub_h, ant_h[k, :, 0], ant_h[k, :, 1])[:, 0]
@@ -368,12 +377,10 @@ def fe_amplitudes(prods, ant, idx, repair: bool = True):
         rows = idx[d_idx, f_idx]
         for k in torch.unique(rows).tolist():
             sel = rows == k
-            dk, fk = d_idx[sel], f_idx[sel]
-            # this sky row's bad columns as a (P, ncols, 5, 1) product set
-            sub_h = prods[:, dk, :, fk].permute(1, 0, 2).unsqueeze(-1)
+            dk, fk = d_idx[sel], f_idx[sel]  # this sky row's bad columns
             ant_h = ant[k].cpu().numpy()
             fe_h, a_h = _assemble_fe_draws(
-                sub_h.cpu().numpy(), ant_h[:, 0], ant_h[:, 1],
+                _host_columns(prods, dk, fk), ant_h[:, 0], ant_h[:, 1],
                 amplitudes=True)
             fe[dk, fk] = torch.as_tensor(
                 fe_h[:, 0], dtype=fe.dtype).to(fe.device)
@@ -390,24 +397,14 @@ def fe_max_pulsars() -> int:
 
 def _null_lfac(prods):
     """(D, F, P, 3) = [l00, l10, l11], the Cholesky factors of the
-    per-pulsar blocks [[ss, sc], [sc, cc]] of ``prods`` (P, D, 5, F), by
-    elementwise torch ops.  Raises ``ValueError`` naming the first
-    (pulsar, draw, frequency) whose block is not positive definite — one
-    ``.any()`` sync."""
-    ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
-    l00 = torch.sqrt(ss)
-    l10 = sc / l00
-    schur = cc - l10 * l10
-    l11 = torch.sqrt(schur)
-    ok = (torch.isfinite(ss) & torch.isfinite(cc) & torch.isfinite(sc)
-          & torch.isfinite(l10) & torch.isfinite(schur) & (ss > 0)
-          & (schur > 0))
-    if bool((~ok).any()):
-        from fastfp_amd.festat import _NOT_PD
+    per-pulsar blocks [[ss, sc], [sc, cc]] of ``prods`` (P, D, 5, F):
+    ``festat._null_factors`` in elementwise torch ops, its ``ValueError``
+    for a block that is not positive definite included — one ``.all()``
+    sync."""
+    from fastfp_amd.festat import _null_factors
 
-        p, d, f = torch.nonzero(~ok)[0].tolist()
-        raise ValueError(_NOT_PD.format(p=p, d=d, f=f))
-    return torch.stack([l00, l10, l11], dim=-1).permute(1, 2, 0, 3).contiguous()
+    return torch.stack(_null_factors(prods, torch),
+                       dim=-1).permute(1, 2, 0, 3).contiguous()
 
 
 def fe_null_skymax(prods, ant, z, repair: bool = True, rtiles: int = 0):
@@ -446,11 +443,9 @@ def fe_null_skymax(prods, ant, z, repair: bool = True, rtiles: int = 0):
             from fastfp_amd.festat import _null_max_host
 
             d_idx, f_idx = torch.nonzero(bad, as_tuple=True)
-            # the bad columns as a (P, ncols, 5, 1) product set
-            sub = prods[:, d_idx, :, f_idx].permute(1, 0, 2).unsqueeze(-1)
-            zsub = z[d_idx, f_idx].unsqueeze(1)  # (ncols, 1, P, 2, R)
-            fm, am = _null_max_host(sub.cpu().numpy(), ant.cpu().numpy(),
-                                    zsub.cpu().numpy())  # (R, ncols, 1)
+            sub_h, z_h = _host_columns(prods, d_idx, f_idx, z)
+            fm, am = _null_max_host(sub_h, ant.cpu().numpy(),
+                                    z_h)  # (R, ncols, 1)
             femax[d_idx, f_idx] = torch.as_tensor(
                 fm[:, :, 0].T.copy(), dtype=femax.dtype).to(femax.device)
             argmax[d_idx, f_idx] = torch.as_tensor(
