@@ -46,6 +46,7 @@ from fastfp_amd.festat import (  # noqa: F401
     cw_amplitudes,
     cw_parameters,
     false_alarm_probability,
+    global_false_alarm,
 )
 from fastfp_amd.nmfp import NMFp  # noqa: F401
 from fastfp_amd.engine import FpEngine  # noqa: F401

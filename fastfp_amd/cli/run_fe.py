@@ -33,6 +33,15 @@ false-alarm probability of each observed maximum,
 normals do not depend on the sky, so under torchrun every rank draws the
 same ones and takes the null maximum over its sky shard; the elementwise
 maximum over ranks is the single-process null.
+
+``--null_joint`` (with ``--null R``) draws the realisations jointly across
+frequencies (``FastFe.null_max(joint=True)``: one noise realisation per
+pulsar serves the whole grid), so ``{savefile}.null.npy`` and
+``{savefile}.pfa.npy`` come from joint realisations, and also writes
+``{savefile}.pfa_global.npy`` = [femax_global, f, pfa_global]
+(``festat.global_false_alarm``): the loudest observed maximum, its
+frequency index, and the probability that noise alone makes any frequency
+that loud.  Under torchrun every rank draws the same ``(w, u)``.
 """
 
 import argparse
@@ -45,7 +54,12 @@ import torch
 
 from fastfp_amd.data import load_pulsars
 from fastfp_amd.engine import FpEngine
-from fastfp_amd.festat import FastFe, cw_parameters, false_alarm_probability
+from fastfp_amd.festat import (
+    FastFe,
+    cw_parameters,
+    false_alarm_probability,
+    global_false_alarm,
+)
 from fastfp_amd.model import get_mats_fp, initialize_pta
 from fastfp_amd.parallel import (
     all_gather_concat,
@@ -90,7 +104,10 @@ def main(
     amplitudes=False,
     null=0,
     null_seed=0,
+    null_joint=False,
 ):
+    if null_joint and not null:
+        raise ValueError("null_joint needs null > 0 realisations")
     if null and not skymax:
         raise ValueError("null needs skymax=True: the null distribution is "
                          "that of the sky maximum")
@@ -174,7 +191,8 @@ def main(
             # every rank draws the same normals (they do not depend on the
             # sky); the maximum over its shard, then over ranks
             nl = (fe.null_max(freqs, local_sky, Nvecs, Ts, sigmas, null,
-                              seed=null_seed, engine=engine)
+                              seed=null_seed, engine=engine,
+                              joint=null_joint)
                   if local_sky else np.full((null, nfreqs), -np.inf))
             nls = all_gather_concat(
                 torch.as_tensor(nl[None], dtype=torch.float64), world, dim=0
@@ -193,6 +211,10 @@ def main(
                 np.save(f"{savefile}.null.npy", nls)
                 np.save(f"{savefile}.pfa.npy",
                         false_alarm_probability(fms[best, cols], nls))
+                if null_joint:
+                    fg, fi, pg = global_false_alarm(fms[best, cols], nls)
+                    np.save(f"{savefile}.pfa_global.npy",
+                            np.array([fg, fi, pg], dtype=np.float64))
             with open(f"{savefile}.json", "w") as f:
                 json.dump({"freqs": [float(x) for x in freqs],
                            "sky": [[t, p] for t, p in sky]}, f)
@@ -251,7 +273,13 @@ def cli():
                              "observed maximum (.pfa.npy)")
     parser.add_argument("--null_seed", type=int, default=0,
                         help="seed of the --null realisations")
+    parser.add_argument("--null_joint", action="store_true",
+                        help="with --null: draw the realisations jointly "
+                             "across frequencies and also write the search-"
+                             "wide false-alarm probability (.pfa_global.npy)")
     args = parser.parse_args()
+    if args.null_joint and not args.null:
+        parser.error("--null_joint requires --null")
     if args.null and not args.skymax:
         parser.error("--null requires --skymax")
     if args.amplitudes and not args.skymax:

@@ -131,6 +131,16 @@ def _eager_products(system: SolveSystem, sigma):
     )
 
 
+def _per_column(A, X):
+    """``A @ X`` for ``A`` (a, k) and ``X`` (k, R), as R independent
+    matrix-vector products (one batch entry each): column r of the result
+    is bitwise the same whatever other columns ``X`` holds, which a
+    single GEMM does not promise."""
+    R = X.shape[1]
+    xt = X.transpose(0, 1).contiguous()[:, :, None]  # (R, k, 1)
+    return torch.bmm(A.expand(R, *A.shape), xt)[:, :, 0].transpose(0, 1)
+
+
 class PulsarBlock:
     """Per-pulsar device tensors + fixed precompute.
 
@@ -201,6 +211,7 @@ class FpEngine:
             PulsarBlock(p.toas, p.residuals, nv, T, self.device)
             for p, nv, T in zip(psrs, Nvecs, Ts)
         ]
+        self.names = [str(getattr(p, "name", i)) for i, p in enumerate(psrs)]
         self.freqs = None
         self._use_hip = False
         self._ext = None  # the HIP extension module, HIP engines only
@@ -988,6 +999,152 @@ class FpEngine:
             for sy, sigma in zip(systems, dense)
         ])  # (P, D, 5, F)
         return out[:, 0] if not batched else out
+
+    # ------------------------------------------------------------------
+    # joint null across frequencies (docs/DESIGN.md section 14)
+    # ------------------------------------------------------------------
+    def null_normals(self, nreal: int, gen):
+        """``(w, u)``: per-pulsar standard normals ``w_p (ntoa_p, nreal)``
+        and ``u_p (m_p, nreal)`` from the ``torch.Generator`` ``gen`` on
+        the engine's device, in pulsar order (w_0, u_0, w_1, ...)."""
+        w, u = [], []
+        for blk in self.blocks:
+            for rows, out in ((blk.ntoa, w), (blk.m, u)):
+                out.append(torch.randn((rows, int(nreal)), generator=gen,
+                                       dtype=torch.float64,
+                                       device=self.device))
+        return w, u
+
+    def _null_kernel_path(self) -> bool:
+        """Whether the joint null runs white term and combine in the HIP
+        kernels: a HIP engine whose direct systems stack."""
+        return self._use_hip and self._direct_stack is not None
+
+    def _null_white(self, w, freq_chunk: int = 2048):
+        """The part of the joint null data that no noise draw changes:
+        ``(white, Tw)`` with ``white_p = w_p^T N^-1/2 S`` and ``Tw_p = T^T
+        N^-1/2 w_p`` (m, R).  Kernel path: ``white`` (P, Rp, 2F+1) as
+        ``sbgemm`` writes it (row r, column 2f+c) and ``Tw`` (P, m, R);
+        otherwise lists of (2F, R) and (m, R) tensors."""
+        assert self.freqs is not None, "call precompute(freqs) first"
+        F = self.freqs.shape[0]
+        white, Tw = [], []
+        for i, (blk, wp) in enumerate(zip(self.blocks, w)):
+            if blk.block_noise is not None:
+                raise NotImplementedError(
+                    f"pulsar {self.names[i]} (index {i}) has block-diagonal "
+                    "white noise (BlockNoise): "
+                    "the joint null needs N^-1/2, implemented for diagonal "
+                    "Nvec only")
+            wp = _t64(wp, self.device)
+            if wp.dim() != 2 or wp.shape[0] != blk.ntoa:
+                raise ValueError(f"w[{i}] must be (ntoa, R) = ({blk.ntoa}, R),"
+                                 f" got {tuple(wp.shape)}")
+            nis = torch.rsqrt(blk.Nvec)
+            nw = nis[:, None] * wp  # (ntoa, R)
+            R = wp.shape[1]
+            if self._null_kernel_path():
+                Tw.append(blk.T.transpose(0, 1) @ nw)
+                zero = torch.zeros(R, dtype=torch.float64, device=self.device)
+                white.append(ops._basis_rhs(wp.contiguous(), nis, blk.toas,
+                                            zero, self.freqs))
+                continue
+            wh = torch.empty((2 * F, R), dtype=torch.float64,
+                             device=self.device)
+            # R independent products: a realisation's value does not
+            # depend on its chunk
+            Tw.append(_per_column(blk.T.transpose(0, 1), nw))
+            for lo in range(0, F, freq_chunk):
+                hi = min(lo + freq_chunk, F)
+                arg = 2.0 * math.pi * self.freqs[lo:hi, None] * blk.toas[None, :]
+                wh[2 * lo:2 * hi:2] = _per_column(torch.sin(arg), nw)
+                wh[2 * lo + 1:2 * hi:2] = _per_column(torch.cos(arg), nw)
+            white.append(wh)
+        if self._null_kernel_path():
+            return torch.stack(white), torch.stack(Tw)
+        return white, Tw
+
+    def _null_combine(self, white_Tw, phiinvs, u):
+        """Joint null data (D, F, P, 2, R) from :meth:`_null_white`'s pair,
+        per-pulsar (D, m) or (m,) ``phiinvs`` and normals ``u_p (m, R)``:
+        ``n = white - B^T Sigma_d^-1 (Tw - phi_d^-1/2 u)``.  Entries of
+        ``phiinvs`` at or below zero (an improper prior, or its rounding
+        when the prior comes back from a dense sigma) count as zero."""
+        white, Tw = white_Tw
+        rows, _ = self._rows(phiinvs)
+        u = [_t64(x, self.device) for x in u]
+        for i, (blk, up) in enumerate(zip(self.blocks, u)):
+            if tuple(up.shape) != (blk.m, Tw[i].shape[1]):
+                raise ValueError(
+                    f"u[{i}] must be (m, R) = ({blk.m}, {Tw[i].shape[1]}), "
+                    f"got {tuple(up.shape)}")
+        P, D, F = len(rows), rows[0].shape[0], self.freqs.shape[0]
+        if self._null_kernel_path():
+            st = self._direct_stack
+            m, R = Tw.shape[1], Tw.shape[2]
+            pinv = torch.stack(rows).contiguous()  # (P, D, m)
+            L, _ = ops.chol_factor(st.A, pinv, ext=self._ext)
+            mp = L.shape[-1]
+            U = torch.zeros((P, D, mp, R), dtype=torch.float64,
+                            device=self.device)
+            U[:, :, :m] = Tw[:, None] - (
+                pinv.clamp_min(0.0).sqrt()[..., None] * torch.stack(u)[:, None])
+            # the solver returns its own (column-major) layout
+            X = torch.cholesky_solve(U.view(P * D, mp, R), L).contiguous()
+            return ops.fe_null_data(white, st.RHS, X.view(P, D, mp, R))
+        R_ = Tw[0].shape[1]
+        n = torch.empty((D, F, P, 2, R_), dtype=torch.float64,
+                        device=self.device)
+        for i, (blk, pinv) in enumerate(zip(self.blocks, rows)):
+            m = blk.m
+            U = Tw[i][None] - pinv.clamp_min(0.0).sqrt()[..., None] * u[i][None]
+            Lc = torch.linalg.cholesky(blk.TNT[None] + torch.diag_embed(pinv))
+            # one solve and one product per realisation, so that a
+            # realisation's value does not depend on its chunk
+            X = torch.cat([torch.cholesky_solve(U[:, :, r:r + 1].contiguous(),
+                                                Lc) for r in range(R_)],
+                          dim=2)  # (D, m, R)
+            Bt = blk.RHS[:m, :2 * F].transpose(0, 1)  # (2F, m)
+            BX = _per_column(Bt, X.permute(1, 0, 2).reshape(m, D * R_))
+            nd = white[i][None] - BX.reshape(2 * F, D, R_).permute(1, 0, 2)
+            n[:, :, i] = nd.reshape(D, F, 2, R_)
+        return n
+
+    def null_data(self, phiinvs, nreal: int, seed: int = 0, w=None, u=None):
+        """Noise-only data products of all frequencies from ONE noise
+        realisation per pulsar: ``n (D, F, P, 2, R)`` with ``n[d, f, p] =
+        (s_f | r)_p, (c_f | r)_p`` for ``r ~ N(0, C_{p,d})``, correlated
+        across frequencies as the data are (docs/DESIGN.md section 14);
+        the layout ``ops.fe_null_skymax`` takes.
+
+        For ``r = N^1/2 w + T phi^1/2 u`` with standard normals ``w``
+        (ntoa) and ``u`` (m),
+
+            n = S^T N^-1/2 w - B^T Sigma^-1 (T^T N^-1/2 w - phi^-1/2 u),
+
+        the engine's own data path on the direct system; ``phi^1/2`` never
+        appears, so an improper prior (``phi^-1 = 0``) contributes exactly
+        nothing.  ``phiinvs``: per-pulsar (m,) or (D, m) prior rows; the
+        SAME ``(w, u)`` serve every draw and every frequency.
+
+        ``w`` / ``u``: lists of (ntoa_p, R) / (m_p, R) normals that
+        bypass the generator; otherwise :meth:`null_normals` draws them
+        from a ``torch.Generator`` of ``seed`` on the engine's device
+        (reproducible per ``(seed, nreal, device type)``).  Diagonal white
+        noise only: a ``BlockNoise`` pulsar raises ``NotImplementedError``.
+        On a HIP engine whose direct systems stack, the white term is the
+        ``sbgemm`` kernel and the combine ``ops.fe_null_data``; otherwise
+        both are torch ops on the engine's device."""
+        assert self.freqs is not None, "call precompute(freqs) first"
+        if (w is None) != (u is None):
+            raise ValueError("give both w and u, or neither")
+        if w is None:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(int(seed))
+            w, u = self.null_normals(nreal, gen)
+        elif any(x.shape[1] != int(nreal) for x in list(w) + list(u)):
+            raise ValueError(f"w and u must hold nreal = {nreal} columns")
+        return self._null_combine(self._null_white(w), phiinvs, u)
 
     @staticmethod
     def _dense(system: SolveSystem, pinv):

@@ -50,7 +50,11 @@ observed maximum into a false-alarm probability, without a solve per
 realisation — for ``r ~ N(0, C)`` the data products of a pulsar are
 exactly ``(sr, cr) ~ N(0, [[ss, sc], [sc, cc]])`` (``ops.fe_null_skymax``
 on a HIP engine, :func:`_null_max_host` otherwise; docs/DESIGN.md
-section 13).
+section 13).  With ``joint=True`` the realisations are drawn jointly
+across frequencies — one noise realisation per pulsar for the whole grid,
+``FpEngine.null_data`` — and :func:`global_false_alarm` gives the
+probability that noise alone makes ANY frequency as loud as the loudest
+observed one (section 14).
 """
 
 from __future__ import annotations
@@ -269,13 +273,29 @@ def _obtain_engine(engine, psrs, freqs, Nvecs, Ts, device, freq_chunk=2048,
     return engine
 
 
-def _phiinvs_from_sigmas(engine, sigmas):
+def _phiinvs_from_sigmas(engine, sigmas, improper=False):
     """Fixed-noise (m, m) sigmas -> per-pulsar diagonal phi^-1 (the
     ``get_mats_fp`` contract sigma = TNT + diag(phi^-1), as in
-    ``FpEngine.sweep``)."""
-    return [(torch.diagonal(_t64(sg, engine.device))
-             - torch.diagonal(blk.TNT)).contiguous()
-            for blk, sg in zip(engine.blocks, sigmas)]
+    ``FpEngine.sweep``).
+
+    The difference knows a prior only to the rounding of ``TNT_kk``, up to
+    ``ntoa eps TNT_kk`` for a sum of ``ntoa`` positive terms.  That is
+    harmless where the prior is added back to ``TNT``; the joint null
+    also takes its square root, which turns rounding of relative size
+    ``1e-16`` into a term of relative size ``1e-8`` that differs from
+    device to device.  With ``improper`` every entry not above ``ntoa eps
+    TNT_kk`` is therefore set to zero, an improper prior: a proper prior
+    that weak moves the data by at most ``sqrt(ntoa eps)`` of their
+    white-noise scatter."""
+    out = []
+    for blk, sg in zip(engine.blocks, sigmas):
+        tnt = torch.diagonal(blk.TNT)
+        p = (torch.diagonal(_t64(sg, engine.device)) - tnt).contiguous()
+        if improper:
+            floor = blk.ntoa * torch.finfo(torch.float64).eps * tnt
+            p = torch.where(p > floor, p, torch.zeros_like(p))
+        out.append(p)
+    return out
 
 
 def _antenna_table(pos, sky, device=None):
@@ -356,13 +376,18 @@ def _ldl4(moments, rcond):
     return ok, (l10, l20, l30, l21, l31, l32, i0, i1, i2, i3)
 
 
-def _null_max_host(prods, ant, z, rcond=1e-12):
+def _null_max_host(prods, ant, z=None, rcond=1e-12, n=None):
     """Host reference of ``ops.fe_null_skymax``: the sky maximum of Fe for
     ``R`` noise-only realisations per (draw, frequency) column.
 
     ``prods`` (P, D, 5, F) (planes ss, cc, sc are read), ``ant``
     (nsky, P, 2), ``z`` (D, F, P, 2, R).  Returns ``(femax (R, D, F),
     argmax (R, D, F) int64)``, the lowest sky index on ties.
+
+    ``n=`` (in place of ``z``, same layout) holds the data products
+    ``(n_s, n_c)`` themselves, e.g. the joint null of
+    ``FpEngine.null_data``: nothing is drawn from the blocks, which are
+    then not checked for positive definiteness.
 
     Per sky point M (the moments of :func:`_assemble_fe_draws`) is
     factored ONCE, elementwise over the columns, and all R realisations
@@ -372,13 +397,20 @@ def _null_max_host(prods, ant, z, rcond=1e-12):
     others are computed with it."""
     prods = np.asarray(prods, dtype=np.float64)
     ant = np.asarray(ant, dtype=np.float64)
-    z = np.asarray(z, dtype=np.float64)
+    if (z is None) == (n is None):
+        raise ValueError("give either z or n")
+    name = "z" if n is None else "n"
+    z = np.asarray(z if n is None else n, dtype=np.float64)
     P, D, _, F = prods.shape
     if z.shape[:4] != (D, F, P, 2):
-        raise ValueError(f"z must be (D, F, P, 2, R) = ({D}, {F}, {P}, 2, R),"
-                         f" got {z.shape}")
+        raise ValueError(f"{name} must be (D, F, P, 2, R) = ({D}, {F}, {P}, "
+                         f"2, R), got {z.shape}")
     R = z.shape[4]
-    ns, nc = _null_draws(prods, z)
+    if n is None:
+        ns, nc = _null_draws(prods, z)
+    else:
+        ns = np.moveaxis(z[:, :, :, 0, :], 2, 0)  # (P, D, F, R)
+        nc = np.moveaxis(z[:, :, :, 1, :], 2, 0)
     femax = np.full((D, F, R), -np.inf)
     argmax = np.full((D, F, R), -1, dtype=np.int64)
     for k in range(ant.shape[0]):
@@ -470,15 +502,39 @@ class _Sky:
         return _assemble_fe_draws(prods, self.ant[k, :, 0], self.ant[k, :, 1],
                                   amplitudes=True)
 
-    def null_max(self, prods, nreal, seed, real_chunk, z=None, gen=None):
+    def null_max(self, prods, nreal, seed, real_chunk, z=None, gen=None,
+                 data=None):
         """(nreal, D, F) null sky maxima of one product set, ``real_chunk``
         realisations at a time.  ``z`` (D, F, P, 2, nreal) bypasses the
         generator; otherwise each chunk is ONE ``torch.randn`` call on the
-        engine's device from ``gen`` (by default a fresh one of ``seed``)."""
+        engine's device from ``gen`` (by default a fresh one of ``seed``).
+        ``data`` (D, F, P, 2, nreal), in place of ``z``, holds the data
+        products ``n`` themselves (``FpEngine.null_data``)."""
         P, D, F = prods.shape[0], prods.shape[1], prods.shape[3]
         nreal, real_chunk = int(nreal), int(real_chunk)
         if nreal < 1 or real_chunk < 1:
             raise ValueError("nreal and real_chunk must be at least 1")
+        if data is not None:
+            if z is not None:
+                raise ValueError("give z or data, not both")
+            if tuple(data.shape) != (D, F, P, 2, nreal):
+                raise ValueError(
+                    f"data must be (D, F, P, 2, nreal) = ({D}, {F}, {P}, 2, "
+                    f"{nreal}), got {tuple(data.shape)}")
+            data = torch.as_tensor(data, dtype=torch.float64)
+            out = np.empty((nreal, D, F))
+            for lo in range(0, nreal, real_chunk):
+                hi = min(lo + real_chunk, nreal)
+                nc = data[..., lo:hi]
+                if self.hip:
+                    fm, _, _ = ops.fe_null_skymax(
+                        prods, self.ant, nc.to(prods.device).contiguous(),
+                        data=True)
+                    out[lo:hi] = fm.cpu().numpy()
+                else:
+                    out[lo:hi] = _null_max_host(prods, self.ant,
+                                                n=nc.cpu().numpy())[0]
+            return out
         if z is not None:
             if tuple(z.shape) != (D, F, P, 2, nreal):
                 raise ValueError(
@@ -504,6 +560,54 @@ class _Sky:
         return out
 
 
+    def null_max_joint(self, engine, chunks, nreal, seed, real_chunk,
+                       w=None, u=None):
+        """(nreal, D, F) null sky maxima drawn JOINTLY across frequencies
+        (docs/DESIGN.md section 14).  ``chunks``: ``(prods, phiinvs)`` per
+        draw chunk, in draw order — the products (P, Dc, 5, F) as this
+        layer takes them and the per-pulsar (Dc, m) or (m,) prior rows
+        they came from.
+
+        Realisation chunks are the OUTER loop: per chunk of ``real_chunk``
+        realisations one ``(w, u)`` per pulsar — ``engine.null_normals``
+        on one generator of ``seed``, or the columns of the explicit
+        ``w`` / ``u`` lists — and one white term serve every draw chunk
+        (common random numbers across noise draws); per draw chunk only
+        ``engine._null_combine`` and the sky maximum run."""
+        nreal, real_chunk = int(nreal), int(real_chunk)
+        if nreal < 1 or real_chunk < 1:
+            raise ValueError("nreal and real_chunk must be at least 1")
+        if (w is None) != (u is None):
+            raise ValueError("give both w and u, or neither")
+        if w is not None and any(
+                x.shape[1] != nreal for x in list(w) + list(u)):
+            raise ValueError(f"w and u must hold nreal = {nreal} columns")
+        gen = None
+        if w is None:
+            gen = torch.Generator(device=engine.device)
+            gen.manual_seed(int(seed))
+        chunks = list(chunks)
+        D = sum(prods.shape[1] for prods, _ in chunks)
+        out = np.empty((nreal, D, chunks[0][0].shape[3]))
+        for lo in range(0, nreal, real_chunk):
+            hi = min(lo + real_chunk, nreal)
+            if gen is not None:
+                wc, uc = engine.null_normals(hi - lo, gen)
+            else:
+                wc = [torch.as_tensor(x)[:, lo:hi] for x in w]
+                uc = [torch.as_tensor(x)[:, lo:hi] for x in u]
+            white = engine._null_white(wc)
+            d0 = 0
+            for prods, phiinvs in chunks:
+                n = engine._null_combine(white, phiinvs, uc)
+                d1 = d0 + prods.shape[1]
+                out[lo:hi, d0:d1] = self.null_max(
+                    prods, hi - lo, seed, hi - lo,
+                    data=n if self.hip else n.cpu())
+                d0 = d1
+        return out
+
+
 def false_alarm_probability(femax, null):
     """False-alarm probability of observed maxima ``femax`` (...) against
     null maxima ``null`` (nreal, ...), ``(1 + #{null >= femax}) / (1 +
@@ -512,6 +616,26 @@ def false_alarm_probability(femax, null):
     null = np.asarray(null)
     return (1.0 + (null >= np.asarray(femax)[None]).sum(axis=0)) \
         / (1.0 + null.shape[0])
+
+
+def global_false_alarm(femax, null):
+    """Search-wide significance of the loudest (sky, frequency) point:
+    ``(femax_global, f_index, pfa_global)`` for observed sky maxima
+    ``femax`` (..., F) and JOINT null sky maxima ``null`` (nreal, ..., F)
+    (``null_max(joint=True)``).  Both sides are maximised over the
+    frequency axis — ``f_index`` is where the observed maximum lies, the
+    lowest index on ties — and ``pfa_global`` is
+    :func:`false_alarm_probability` of the one against the other: ties
+    count, and it is never zero.  With a null drawn independently per
+    frequency the result is not a probability of anything."""
+    femax = np.asarray(femax)
+    null = np.asarray(null)
+    if femax.ndim < 1 or null.shape[1:] != femax.shape:
+        raise ValueError(f"null must be (nreal,) + femax.shape = (nreal, "
+                         f"{femax.shape}), got {null.shape}")
+    fg = femax.max(axis=-1)
+    return fg, femax.argmax(axis=-1), \
+        false_alarm_probability(fg, null.max(axis=-1))
 
 
 class FastFe:
@@ -636,7 +760,8 @@ class FastFe:
     # ------------------------------------------------------------------
     def null_max(self, freqs, sky, Nvecs, Ts, sigmas, nreal: int,
                  seed: int = 0, device: str = None, engine: FpEngine = None,
-                 real_chunk: int = 256, z=None) -> np.ndarray:
+                 real_chunk: int = 256, z=None, joint: bool = False,
+                 w=None, u=None) -> np.ndarray:
         """The sky-maximised Fe of ``nreal`` noise-only realisations per
         frequency: ``(nreal, F)``, the Monte-Carlo null distribution of
         what :meth:`sweep_max` returns.
@@ -658,19 +783,46 @@ class FastFe:
         normals of shape (1, F, P, 2, nreal) and bypasses the generator
         (the result then does not depend on ``real_chunk``).
 
-        Scope.  The null is exact per frequency.  Realisations are drawn
-        independently per frequency, so the joint distribution across
-        frequencies is not modelled and a trials factor over frequency is
-        out of scope; so is a signal-present mean for detection-
-        probability curves.
+        Scope.  The null is exact per frequency.  By default realisations
+        are drawn independently per frequency, so the joint distribution
+        across frequencies is not modelled.  ``joint=True`` draws ONE
+        noise realisation per pulsar for all frequencies
+        (``FpEngine.null_data``, docs/DESIGN.md section 14; diagonal white
+        noise only): row ``r`` of the result is then one noise-only data
+        set seen at every frequency, which is what
+        :func:`global_false_alarm` needs.  Its normals come from one
+        generator of ``seed`` per ``real_chunk`` (reproducible per
+        ``(seed, real_chunk, device type)``), or from the explicit lists
+        ``w`` ((ntoa_p, nreal) each) and ``u`` ((m_p, nreal) each).  A
+        signal-present mean for detection-probability curves is out of
+        scope.
         """
+        if joint:
+            if z is not None:
+                raise ValueError("joint=True takes w= and u=, not z=")
+            engine = _obtain_engine(engine, self.psrs, freqs, Nvecs, Ts,
+                                    device)
+        elif w is not None or u is not None:
+            raise ValueError("w= and u= need joint=True")
         layer, prods = self._setup(freqs, sky, Nvecs, Ts, sigmas, device,
                                    engine)
-        return layer.null_max(prods, nreal, seed, real_chunk, z)[:, 0, :]
+        return self._null(layer, prods, engine, sigmas, nreal, seed,
+                          real_chunk, z, joint, w, u)
+
+    @staticmethod
+    def _null(layer, prods, engine, sigmas, nreal, seed, real_chunk, z,
+              joint, w, u):
+        """(nreal, F) null maxima of the one-draw product set ``prods``."""
+        if not joint:
+            return layer.null_max(prods, nreal, seed, real_chunk, z)[:, 0, :]
+        chunk = (prods, _phiinvs_from_sigmas(engine, sigmas, improper=True))
+        return layer.null_max_joint(engine, [chunk], nreal, seed, real_chunk,
+                                    w, u)[:, 0, :]
 
     def false_alarm(self, freqs, sky, Nvecs, Ts, sigmas, nreal: int,
                     seed: int = 0, device: str = None, engine: FpEngine = None,
-                    real_chunk: int = 256, z=None):
+                    real_chunk: int = 256, z=None, joint: bool = False,
+                    w=None, u=None):
         """The observed sky maximum and its false-alarm probability:
         ``(femax (F,), argmax (F,), pfa (F,))`` with ``femax, argmax`` as
         :meth:`sweep_max` returns them and
@@ -681,12 +833,28 @@ class FastFe:
         :meth:`null_max` (same arguments, same stream, same scope: a
         single-frequency probability, no trials factor over frequency).
         The products and the antenna table are computed once and serve
-        both passes."""
+        both passes.
+
+        ``joint=True``: the null is drawn jointly across frequencies
+        (:meth:`null_max`), ``pfa`` comes from those realisations, and the
+        result grows to ``(femax, argmax, pfa, femax_global, fglobal,
+        pfa_global)``: the loudest observed maximum over the grid, its
+        frequency index, and the probability that noise alone makes ANY
+        frequency that loud (:func:`global_false_alarm`)."""
+        if joint:
+            if z is not None:
+                raise ValueError("joint=True takes w= and u=, not z=")
+            engine = _obtain_engine(engine, self.psrs, freqs, Nvecs, Ts,
+                                    device)
+        elif w is not None or u is not None:
+            raise ValueError("w= and u= need joint=True")
         layer, prods = self._setup(freqs, sky, Nvecs, Ts, sigmas, device,
                                    engine)
         femax, argmax = (x[0] for x in layer.max(prods))
-        null = layer.null_max(prods, nreal, seed, real_chunk, z)[:, 0, :]
-        return femax, argmax, false_alarm_probability(femax, null)
+        null = self._null(layer, prods, engine, sigmas, nreal, seed,
+                          real_chunk, z, joint, w, u)
+        out = (femax, argmax, false_alarm_probability(femax, null))
+        return out + global_false_alarm(femax, null) if joint else out
 
 
 def compute_Fe(psrs, pta, noise, freqs, sky, device=None) -> np.ndarray:
@@ -804,7 +972,8 @@ class NMFe:
     def null_max(self, freqs, sky, samples: dict, Nvecs, Ts, nreal: int,
                  seed: int = 0, draw_chunk: int = 8, real_chunk: int = 128,
                  engine: FpEngine = None, compress: bool = False,
-                 device: str = None) -> np.ndarray:
+                 device: str = None, joint: bool = False, w=None,
+                 u=None) -> np.ndarray:
         """:meth:`FastFe.null_max` over noise draws: ``(nreal, D, F)``,
         the sky-maximised Fe of ``nreal`` noise-only realisations for
         every (draw, frequency), each draw's realisations drawn from that
@@ -817,9 +986,34 @@ class NMFe:
         holds the M factors of ``draw_chunk * F * nsky`` points (80 bytes
         each) and ``draw_chunk * F * P * 2 * real_chunk`` normals, which
         is what the two chunk sizes bound.  Scope as in
-        :meth:`FastFe.null_max`."""
+        :meth:`FastFe.null_max`.
+
+        ``joint=True``: realisations are drawn jointly across frequencies
+        as in :meth:`FastFe.null_max` (``w`` / ``u`` likewise).  The
+        products of all draw chunks are kept (5 F doubles per pulsar and
+        draw) and the realisation chunks become the outer loop, so one
+        ``(w, u)`` and one white term per realisation chunk serve EVERY
+        noise draw: common random numbers across draws — realisation
+        ``r`` is the same white and basis normals coloured by each draw's
+        prior, which removes Monte-Carlo scatter from draw-to-draw
+        comparisons and leaves each draw's own null exact.  The data
+        always go through the direct system (``compress`` only chooses
+        where the products come from).  The stream is reproducible per
+        ``(seed, real_chunk, device type)`` and does not depend on
+        ``draw_chunk``."""
         engine, layer = self._layer(freqs, sky, samples, Nvecs, Ts, device,
                                     engine, compress)
+        if joint:
+            phiinvs = batch_phiinv(self.rn_sigs, samples)
+            phiinvs = [p[None, :] if p.dim() == 1 else p for p in phiinvs]
+            rows = [[p[lo:lo + draw_chunk] for p in phiinvs]
+                    for lo in range(0, phiinvs[0].shape[0], draw_chunk)]
+            prods = self._draw_chunks(engine, samples, draw_chunk, compress,
+                                      layer.hip)
+            return layer.null_max_joint(engine, zip(prods, rows), nreal, seed,
+                                        real_chunk, w, u)
+        if w is not None or u is not None:
+            raise ValueError("w= and u= need joint=True")
         gen = torch.Generator(device=engine.device)
         gen.manual_seed(int(seed))
         return np.concatenate([

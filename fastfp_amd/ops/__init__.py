@@ -407,7 +407,44 @@ def _null_lfac(prods):
                        dim=-1).permute(1, 2, 0, 3).contiguous()
 
 
-def fe_null_skymax(prods, ant, z, repair: bool = True, rtiles: int = 0):
+def fe_null_data(white, rhs, X, out=None):
+    """Joint null data of the Fe statistic on the device (docs/DESIGN.md
+    section 14): ``n[d, f, p, c, r] = white[p, r, 2f+c] - sum_k rhs[p, k,
+    2f+c] X[p, d, k, r]``, one fp64 MFMA GEMM per (pulsar, draw).
+
+    ``white`` (P, Rp, ldw), ``Rp >= R`` and ``ldw >= 2F``, as ``sbgemm``
+    writes it (the kernel transposes it); ``rhs`` (P, mp, 2F+1), the
+    engine's stacked RHS, last column not read, ``mp`` a multiple of 16
+    up to 256; ``X`` (P, D, mp, R) with zero padding rows.  Returns the
+    contiguous (D, F, P, 2, R) tensor ``fe_null_skymax`` takes as
+    ``z``, written into ``out`` when given."""
+    ext = _fe_ext()
+    P, D, R = X.shape[0], X.shape[1], X.shape[3]
+    F = (rhs.shape[2] - 1) // 2
+    if out is None:
+        out = torch.empty((D, F, P, 2, R), dtype=torch.float64,
+                          device=X.device)
+    ext.fe_null_data(white, rhs, X, out)
+    return out
+
+
+def fe_null_data_torch(white, rhs, X):
+    """What :func:`fe_null_data` computes, in torch ops: ``baddbmm`` per
+    draw and a permuting copy into (D, F, P, 2, R).  The comparison arm
+    of the measurement in docs/PERFORMANCE.md ("Fe joint null")."""
+    P, D, R = X.shape[0], X.shape[1], X.shape[3]
+    F = (rhs.shape[2] - 1) // 2
+    wt = white[:, :R, :2 * F].transpose(1, 2)  # (P, 2F, R)
+    Bt = rhs[:, :, :2 * F].transpose(1, 2)  # (P, 2F, mp)
+    out = torch.empty((D, F, P, 2, R), dtype=torch.float64, device=X.device)
+    for d in range(D):
+        nd = torch.baddbmm(wt, Bt, X[:, d], alpha=-1.0)  # (P, 2F, R)
+        out[d] = nd.reshape(P, F, 2, R).permute(1, 0, 2, 3)
+    return out
+
+
+def fe_null_skymax(prods, ant, z, repair: bool = True, rtiles: int = 0,
+                   data: bool = False):
     """The sky maximum of Fe for ``R`` noise-only realisations per (draw,
     frequency) column, on the device (docs/DESIGN.md section 13).
 
@@ -429,13 +466,23 @@ def fe_null_skymax(prods, ant, z, repair: bool = True, rtiles: int = 0):
     ``festat._null_max_host`` (pseudo-inverse at the degenerate points);
     ``nskip`` keeps the kernel's counts.  ``rtiles``: realisation tiles
     per workgroup (a tuning knob; no result depends on it).
+
+    ``data``: ``z`` holds the data products ``n`` themselves, ``z[d, f, p]
+    = (n_s, n_c)`` (the joint null of ``FpEngine.null_data``, section 14).
+    The same kernel runs with the factor ``(1, 0, 1)``, under which ``n_s
+    = 1 * z0`` and ``n_c = fma(0, z0, 1 * z1)`` are exact; the blocks are
+    not factored and so not checked for positive definiteness.
     """
     ext = _fe_ext()
     if prods.dim() != 4 or prods.shape[2] != 5:
         raise RuntimeError("prods must be (P, D, 5, F)")
     prods = prods.contiguous()
     ant = ant.contiguous()
-    lfac = _null_lfac(prods)
+    if data:
+        P, D, F = prods.shape[0], prods.shape[1], prods.shape[3]
+        lfac = prods.new_tensor([1.0, 0.0, 1.0]).expand(D, F, P, 3).contiguous()
+    else:
+        lfac = _null_lfac(prods)
     femax, argmax, nskip = ext.fe_null_skymax(prods, ant, lfac, z, rtiles)
     if repair:
         bad = nskip > 0
@@ -445,7 +492,8 @@ def fe_null_skymax(prods, ant, z, repair: bool = True, rtiles: int = 0):
             d_idx, f_idx = torch.nonzero(bad, as_tuple=True)
             sub_h, z_h = _host_columns(prods, d_idx, f_idx, z)
             fm, am = _null_max_host(sub_h, ant.cpu().numpy(),
-                                    z_h)  # (R, ncols, 1)
+                                    **{"n" if data else "z": z_h}
+                                    )  # (R, ncols, 1)
             femax[d_idx, f_idx] = torch.as_tensor(
                 fm[:, :, 0].T.copy(), dtype=femax.dtype).to(femax.device)
             argmax[d_idx, f_idx] = torch.as_tensor(

@@ -549,6 +549,50 @@ std::vector<torch::Tensor> fe_null_skymax(torch::Tensor prods,
   return {femax, argmax, nskip};
 }
 
+// fe_null_data: joint null data n = white^T - rhs^T X per (pulsar, draw),
+// written into `out` (D, F, P, 2, R), the z layout of fe_null_skymax.
+// white (P, Rp, ldw) is taken AS sbgemm WRITES IT, white[p][r][2f+c] with
+// Rp >= R rows and ldw >= 2F columns: the kernel transposes it while it
+// loads the accumulators.  rhs (P, mp, 2F+1) is the engine's stacked RHS
+// (last column not read); X (P, D, mp, R) must hold zeros in the padding
+// rows.  `out` may be a larger buffer's leading part: exactly its
+// D*F*P*2*R entries are written.
+void fe_null_data(torch::Tensor white, torch::Tensor rhs, torch::Tensor X,
+                  torch::Tensor out) {
+  check_f64(white, "white");
+  check_f64(rhs, "rhs");
+  check_f64(X, "X");
+  check_f64(out, "out");
+  TORCH_CHECK(white.device() == rhs.device() && X.device() == rhs.device() &&
+                  out.device() == rhs.device(),
+              "white/rhs/X/out device mismatch");
+  TORCH_CHECK(rhs.dim() == 3 && rhs.size(2) >= 1 && rhs.size(2) % 2 == 1,
+              "rhs must be (P, mp, 2F+1)");
+  const int64_t P = rhs.size(0), mp = rhs.size(1), F = (rhs.size(2) - 1) / 2;
+  TORCH_CHECK(mp % 16 == 0 && mp >= 16 && mp <= 256,
+              "fe_null_data supports mp = a multiple of 16 up to 256; got ",
+              mp);
+  TORCH_CHECK(X.dim() == 4 && X.size(0) == P && X.size(2) == mp,
+              "X must be (P, D, mp, R) matching rhs");
+  const int64_t D = X.size(1), R = X.size(3);
+  TORCH_CHECK(white.dim() == 3 && white.size(0) == P && white.size(1) >= R &&
+                  white.size(2) >= 2 * F,
+              "white must be (P, Rp >= R, ldw >= 2F) matching rhs and X");
+  TORCH_CHECK(out.dim() == 5 && out.size(0) == D && out.size(1) == F &&
+                  out.size(2) == P && out.size(3) == 2 && out.size(4) == R,
+              "out must be (D, F, P, 2, R)");
+  TORCH_CHECK(P < (1L << 31) && D < (1L << 31) && F < (1L << 30) &&
+                  R < (1L << 31) && white.size(1) < (1L << 31) &&
+                  white.size(2) < (1L << 31),
+              "dimension overflow");
+  check_launch(
+      launch_fe_null_data(white.data_ptr<double>(), rhs.data_ptr<double>(),
+                          X.data_ptr<double>(), (int)P, (int)D, (int)F, (int)R,
+                          (int)white.size(1), (int)white.size(2), (int)mp,
+                          out.data_ptr<double>(), stream()),
+      "fe_null_data");
+}
+
 // diag_inv: invert the 16x16 diagonal blocks of batched lower-tri L
 // (B, mp, mp) -> invd (B, mp/16, 16, 16); the m > 128 direct path.
 torch::Tensor diag_inv(torch::Tensor L) {
@@ -641,6 +685,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "sky maximum of Fe over noise-only realisations n = L z",
         py::arg("prods"), py::arg("ant"), py::arg("lfac"), py::arg("z"),
         py::arg("rtiles") = 0);
+  m.def("fe_null_data", &fe_null_data,
+        "joint null data n = white^T - rhs^T X into (D, F, P, 2, R)",
+        py::arg("white"), py::arg("rhs"), py::arg("X"), py::arg("out"));
   m.def("fe_max_pulsars", &fe_max_pulsars,
         "largest pulsar count of the Fe sky kernels");
 }

@@ -764,7 +764,150 @@ static hipError_t fe_null_launch(const double* ant, const double* lfac,
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------
+// Joint null data across frequencies (docs/DESIGN.md section 14).
+//
+//   n[d, f, p, c, r] = white[p, r, 2f+c] - sum_k rhs[p, k, 2f+c] X[p, d, k, r]
+//
+// a batched fp64 GEMM over (pulsar, draw) with M = 2F rows (2f+c), N = R
+// columns (realisations) and K = mp, in the operand layout at the top of
+// this file: a = -rhs[k][row], b = X[k][col], acc = C[row][col].  The
+// accumulators START from the white tile (read transposed: white is
+// (r, 2f+c) as sbgemm writes it) and the factor's columns enter negated,
+// so the MFMA chain IS the subtraction.
+//
+// One workgroup (4 waves) owns a 64 x 64 tile of one (pulsar, draw): wave
+// w the 16 rows 16w.. and all four 16-column tiles, so one a operand
+// feeds four MFMAs.  K runs in chunks of 16 staged through LDS as
+// As[4][16][16] / Bs[4][16][16] (tile, k, 16): a wave's operand read is 4
+// k rows x 16 contiguous doubles, conflict-free as in fe_sky_kernel.  The
+// next chunk's 8 doubles per thread are loaded into registers before the
+// MFMAs of the current one.  Global loads are contiguous in the row index
+// (rhs) and in r (X); rows >= 2F (the last column of rhs is never read)
+// and columns >= R are loaded as zero and not stored.  The epilogue
+// writes (D, F, P, 2, R) directly: lane l holds column r = l & 15, so a
+// row is stored as contiguous 128-byte runs in R.  Fixed k order, no
+// atomics: bitwise reproducible.  Static LDS 16 KiB.
+// ---------------------------------------------------------------------
+#define FND_TILE 64
+#define FND_KC 16
+
+__global__ __launch_bounds__(FE_THREADS) void fe_null_data_kernel(
+    const double* __restrict__ white /*(P, Rp, ldw)*/,
+    const double* __restrict__ rhs /*(P, mp, ldr)*/,
+    const double* __restrict__ X /*(P, D, mp, R)*/, int P, int D, int F,
+    int R, int mp, long wstride /*Rp * ldw*/, int ldw, int ldr, int mtiles,
+    int ntiles, double* __restrict__ out /*(D, F, P, 2, R)*/) {
+  __shared__ double As[4][FND_KC][16];
+  __shared__ double Bs[4][FND_KC][16];
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = tid >> 6;
+  const int li = lane & 15;  // a row within the wave's tile / b,acc column
+  const int lk = lane >> 4;  // k index / acc row group
+  const int F2 = 2 * F;
+
+  long b = blockIdx.x;
+  const int nt = (int)(b % ntiles);
+  b /= ntiles;
+  const int mt = (int)(b % mtiles);
+  b /= mtiles;
+  const int d = (int)(b % D);
+  const int p = (int)(b / D);
+  const int M0 = mt * FND_TILE;
+  const int N0 = nt * FND_TILE;
+
+  const double* rp = rhs + (long)p * mp * ldr;
+  const double* xp = X + ((long)p * D + d) * mp * R;
+  const double* wp = white + (long)p * wstride;
+
+  // staging: element e = tid + 256 i of a chunk is (k = e / 64, j = e % 64)
+  const int sj = tid & 63;
+  const int sk = tid >> 6;  // k = sk + 4 i
+  const bool aok = M0 + sj < F2;
+  const bool bok = N0 + sj < R;
+  const double* ag = rp + (long)sk * ldr + M0 + sj;
+  const double* bg = xp + (long)sk * R + N0 + sj;
+
+  double ra[4], rb[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ra[i] = aok ? ag[(long)(4 * i) * ldr] : 0.0;
+    rb[i] = bok ? bg[(long)(4 * i) * R] : 0.0;
+  }
+
+  // accumulators from the white tile: acc[t][v] = C[row 4v + lk][col li]
+  f64x4 acc[4];
+  const int row0 = M0 + 16 * wv;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int r = N0 + 16 * t + li;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int row = row0 + 4 * v + lk;
+      acc[t][v] = (r < R && row < F2) ? wp[(long)r * ldw + row] : 0.0;
+    }
+  }
+
+  const int nch = mp / FND_KC;
+  for (int ch = 0; ch < nch; ++ch) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      As[sj >> 4][sk + 4 * i][sj & 15] = -ra[i];
+      Bs[sj >> 4][sk + 4 * i][sj & 15] = rb[i];
+    }
+    __syncthreads();
+    if (ch + 1 < nch) {
+      const long k0 = (long)(ch + 1) * FND_KC;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        ra[i] = aok ? ag[(k0 + 4 * i) * ldr] : 0.0;
+        rb[i] = bok ? bg[(k0 + 4 * i) * R] : 0.0;
+      }
+    }
+#pragma unroll
+    for (int ks = 0; ks < FND_KC / 4; ++ks) {
+      const double a = As[wv][4 * ks + lk][li];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        acc[t] = MFMA_F64(a, Bs[t][4 * ks + lk][li], acc[t]);
+    }
+    __syncthreads();
+  }
+
+#pragma unroll
+  for (int v = 0; v < 4; ++v) {
+    const int row = row0 + 4 * v + lk;
+    if (row >= F2) continue;
+    const long f = row >> 1, c = row & 1;
+    double* op = out + ((((long)d * F + f) * P + p) * 2 + c) * R;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int r = N0 + 16 * t + li;
+      if (r < R) op[r] = acc[t][v];
+    }
+  }
+}
+
 extern "C" {
+
+int launch_fe_null_data(const double* white, const double* rhs,
+                        const double* X, int P, int D, int F, int R, int Rp,
+                        int ldw, int mp, double* out, hipStream_t stream) {
+  if (P == 0 || D == 0 || F == 0 || R == 0) return (int)hipSuccess;
+  if (mp < 16 || mp > 256 || mp % 16 != 0 || Rp < R || ldw < 2 * F)
+    return (int)hipErrorInvalidValue;
+  const long mtiles = (2L * F + FND_TILE - 1) / FND_TILE;
+  const long ntiles = ((long)R + FND_TILE - 1) / FND_TILE;
+  const long nblk = (long)P * D * mtiles * ntiles;
+  if (nblk > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(fe_null_data_kernel, dim3((unsigned)nblk),
+                     dim3(FE_THREADS), 0, stream, white, rhs, X, P, D, F, R,
+                     mp, (long)Rp * ldw, ldw, 2 * F + 1, (int)mtiles,
+                     (int)ntiles, out);
+  return (int)hipGetLastError();
+}
 
 // Largest P the resident product tile supports: 5 * Kp * 16 doubles of
 // dynamic LDS next to the static reduction slots, within 160 KiB.

@@ -136,4 +136,14 @@ int launch_fe_null_skymax(const double* prods, const double* ant,
                           double* femax, int* argmax, int* nskip,
                           hipStream_t stream);
 
+// Joint null data: white (P,Rp,ldw) with white[p][r][2f+c] (the kernel
+// transposes it), rhs (P,mp,2F+1) whose last column is not read, X
+// (P,D,mp,R) with zero padding rows -> out (D,F,P,2,R) =
+// white[p][r][2f+c] - sum_k rhs[p][k][2f+c] X[p][d][k][r].  mp = any
+// multiple of 16 up to 256; Rp >= R, ldw >= 2F.  Every entry of out is
+// written, nothing else.
+int launch_fe_null_data(const double* white, const double* rhs,
+                        const double* X, int P, int D, int F, int R, int Rp,
+                        int ldw, int mp, double* out, hipStream_t stream);
+
 }  // extern "C"

@@ -27,6 +27,19 @@ R = 1024 realisations, with 1, 2 and 4 realisation tiles per workgroup,
 and its factor pass fe_mfactor alone) in rounds alternated with the route
 that needs no new kernel: fe_skymax on products replicated to (P, R, 5, F)
 with the realisations in the planes sr, cr.
+
+    python tools/kernel_bench.py nulldata [P D F R m]
+
+times the joint-null combine (fe_null_data) in rounds alternated with
+the torch route to the same array (baddbmm + permuting copy); defaults
+P=67, D=1, F=200, R=1024, m=120.
+
+    python tools/kernel_bench.py nulljoint [npsr ntoa F nsky R]
+
+times FastFe.null_max with joint=True and joint=False in alternated
+rounds on the synthetic bench array (m = 120), and the phases of one
+joint chunk (normals, white-term sbgemm, factor + solve, fe_null_data,
+sky kernel); defaults npsr=67, ntoa=5000, F=200, nsky=768, R=1024.
 """
 
 import sys
@@ -375,8 +388,143 @@ def main_fe_null(P, F, nsky, ant, rng, R=1024, rounds=5):
               f"max {max(v)*1e3:.3f})")
 
 
+def _rounds(arms, rounds, iters, warmup=2):
+    """Alternated rounds of ``arms`` (name -> callable): name -> list of
+    per-call seconds, one entry per round."""
+    ts = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            ts[k].append(timeit(fn, iters=iters, warmup=warmup))
+    return ts
+
+
+def _report(tag, v, extra=""):
+    print(f"{tag}: median {float(np.median(v))*1e3:9.3f} ms  ({len(v)} "
+          f"rounds: min {min(v)*1e3:.3f}, max {max(v)*1e3:.3f}){extra}")
+
+
+def main_null_data(P=67, D=1, F=200, R=1024, m=120, rounds=5):
+    """fe_null_data against baddbmm + permuting copy, same inputs, same
+    output array."""
+    from fastfp_amd import ops
+
+    rng = np.random.default_rng(0)
+    mp = ops.pad16(m)
+    Rp = ops.pad16(R)
+    white = torch.as_tensor(rng.normal(size=(P, Rp, 2 * F + 1)), device=DEV)
+    rhs = torch.as_tensor(rng.normal(size=(P, mp, 2 * F + 1)), device=DEV)
+    X = torch.zeros((P, D, mp, R), dtype=torch.float64, device=DEV)
+    X[:, :, :m] = torch.as_tensor(rng.normal(size=(P, D, m, R)), device=DEV)
+    out = torch.empty((D, F, P, 2, R), dtype=torch.float64, device=DEV)
+    a = ops.fe_null_data(white, rhs, X, out=out)
+    b = ops.fe_null_data_torch(white, rhs, X)
+    rel = float(((a - b).abs().max() / b.abs().max()))
+    print(f"check: fe_null_data vs torch max abs diff / max abs {rel:.2e}")
+    assert rel < 1e-12
+    del a, b
+    ts = _rounds({
+        "fe_null_data": lambda: ops.fe_null_data(white, rhs, X, out=out),
+        "torch baddbmm+copy": lambda: ops.fe_null_data_torch(white, rhs, X),
+    }, rounds, iters=300, warmup=10)
+    nbytes = 2.0 * out.numel() * 8  # white read + n written
+    flops = 2.0 * P * D * 2 * F * R * mp
+    for k, v in ts.items():
+        t = float(np.median(v))
+        _report(f"{k:20s} P={P} D={D} F={F} R={R} mp={mp}", v,
+                f"  {nbytes/t/1e9:7.1f} GB/s (white + n), "
+                f"{flops/t/1e12:5.2f} TF/s")
+
+
+def main_null_joint(npsr=67, ntoa=5000, F=200, nsky=768, R=1024, rounds=3):
+    """null_max(joint=True) against null_max(joint=False), and the phases
+    of one joint chunk, on the synthetic bench array."""
+    import time
+
+    from fastfp_amd import FastFe, FpEngine, initialize_pta, ops
+    from fastfp_amd.cli.run_fe import fibonacci_sky
+    from fastfp_amd.data import make_synthetic_pta
+    from fastfp_amd.festat import _phiinvs_from_sigmas
+    from fastfp_amd.model import get_mats_fp
+
+    psrs = make_synthetic_pta(npsr=npsr, ntoa=ntoa, ntm=60, seed=0)
+    noise = {"gw_gamma": 13.0 / 3.0, "gw_log10_A": float(np.log10(2e-15))}
+    for p in psrs:
+        noise[f"{p.name}_red_noise_gamma"] = 4.0
+        noise[f"{p.name}_red_noise_log10_A"] = -14.5
+    pta = initialize_pta(psrs, noise, inc_cp=True, rn_comps=30, gwb_comps=30)
+    Nvecs, Ts, sigmas = get_mats_fp(pta, noise)
+    freqs = np.linspace(2e-9, 3e-7, F)
+    sky = fibonacci_sky(nsky)
+    eng = FpEngine(psrs, Nvecs, Ts, device=DEV)
+    eng.precompute(freqs)
+    assert eng._null_kernel_path()
+    fe = FastFe(psrs, pta)
+    args = (freqs, sky, Nvecs, Ts, sigmas, R)
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    arms = {
+        "null_max joint=False": lambda: fe.null_max(
+            *args, seed=1, engine=eng, real_chunk=R),
+        "null_max joint=True": lambda: fe.null_max(
+            *args, seed=1, engine=eng, real_chunk=R, joint=True),
+    }
+    for fn in arms.values():
+        fn()  # warm-up
+    ts = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            ts[k].append(wall(fn)[0])
+    for k, v in ts.items():
+        _report(f"{k:22s} P={npsr} F={F} nsky={nsky} R={R}", v)
+
+    # the phases of one joint chunk, each ended by a synchronise
+    layer, prods = fe._setup(freqs, sky, Nvecs, Ts, sigmas, DEV, eng)
+    phiinvs = _phiinvs_from_sigmas(eng, sigmas, improper=True)
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(1)
+    st = eng._direct_stack
+    ph = {k: [] for k in ("normals", "white sbgemm + Tw", "factor + solve",
+                          "fe_null_data", "sky kernel")}
+    for i in range(rounds + 1):
+        t_n, (w, u) = wall(lambda: eng.null_normals(R, gen))
+        t_w, (white, Tw) = wall(lambda: eng._null_white(w))
+
+        def solve():
+            pinv = torch.stack(eng._rows(phiinvs)[0]).contiguous()
+            L, _ = ops.chol_factor(st.A, pinv, ext=eng._ext)
+            mp, m = L.shape[-1], Tw.shape[1]
+            U = torch.zeros((npsr, 1, mp, R), dtype=torch.float64, device=DEV)
+            U[:, :, :m] = Tw[:, None] - (pinv.clamp_min(0.0).sqrt()[..., None]
+                                         * torch.stack(u)[:, None])
+            return torch.cholesky_solve(U.view(npsr, mp, R), L).contiguous()
+
+        t_s, X = wall(solve)
+        t_c, n = wall(lambda: ops.fe_null_data(
+            white, st.RHS, X.view(npsr, 1, -1, R)))
+        t_k, _ = wall(lambda: ops.fe_null_skymax(prods, layer.ant, n,
+                                                 data=True))
+        if i:  # the first pass warms up
+            for k, t in zip(ph, (t_n, t_w, t_s, t_c, t_k)):
+                ph[k].append(t)
+        del w, u, white, Tw, X, n
+    total = sum(float(np.median(v)) for v in ph.values())
+    for k, v in ph.items():
+        _report(f"phase {k:20s}", v,
+                f"  {float(np.median(v)) / total * 100:5.1f} % of the phases")
+
+
 if __name__ == "__main__":
-    if len(sys.argv) > 1 and sys.argv[1] == "fe":
+    if len(sys.argv) > 1 and sys.argv[1] == "nulldata":
+        main_null_data(*[int(a) for a in sys.argv[2:]])
+    elif len(sys.argv) > 1 and sys.argv[1] == "nulljoint":
+        main_null_joint(*[int(a) for a in sys.argv[2:]])
+    elif len(sys.argv) > 1 and sys.argv[1] == "fe":
         main_fe(*[int(a) for a in sys.argv[2:]])
     elif len(sys.argv) > 1 and sys.argv[1] == "factor":
         main_factor(*[int(a) for a in sys.argv[2:]])
