@@ -1,4 +1,4 @@
-"""Extended-precision oracle for the solve and precompute kernels.
+"""Extended-precision oracle for the solve, precompute and Fe kernels.
 
 Plain numpy in ``np.longdouble`` (x87 80-bit, 64-bit significand):
 every kernel-level GPU test compares a HIP kernel with these functions
@@ -12,7 +12,8 @@ O(m^3) / O(m^2 n) interpreted loops over longdouble vector operations.
 
 The second half of the module holds the input generators the GPU tests
 share (``gen_sigma``, ``gen_rhs``, ``gen_closure``, ``gen_trig``,
-``gen_blocks``); ``tests/test_hpref.py`` checks both halves on the CPU.
+``gen_blocks``, ``gen_fe_case``) and the cached cases built from them;
+``tests/test_hpref.py`` checks both halves on the CPU.
 """
 
 import numpy as np
@@ -218,6 +219,146 @@ def block_dots(toas, uvec, nr, freqs, beta, offsets, sizes, dtype=LD):
 
 
 # ----------------------------------------------------------------------
+# the Fe sky kernels (fe_kernels.hip)
+# ----------------------------------------------------------------------
+def fe_sums(prods, ant):
+    """The sums over pulsars of one Fe point: M (D, nsky, F, 10), the ten
+    unique entries (m00, m01, m02, m03, m11, m12, m13, m22, m23, m33) of
+    the symmetric 4x4 M over the filters F+ sin, F+ cos, Fx sin, Fx cos,
+    and N (D, nsky, F, 4).  ``prods`` (P, D, 5, F) = [ss, cc, sc, sr, cr],
+    ``ant`` (nsky, P, 2) = [F+, Fx]; the coefficient products F+^2, F+ Fx,
+    Fx^2 are formed in longdouble too."""
+    prods, ant = _ld(prods), _ld(ant)
+    P, D, _, F = prods.shape
+    fp, fx = ant[:, :, 0], ant[:, :, 1]  # (nsky, P)
+    ss, cc, sc, sr, cr = (prods[:, :, i].reshape(P, D * F) for i in range(5))
+
+    def psum(coeff, q):  # (nsky, P) x (P, D F) -> (D, nsky, F)
+        return np.moveaxis((coeff @ q).reshape(-1, D, F), 0, 1)
+
+    p2, px, x2 = fp * fp, fp * fx, fx * fx
+    pxsc = psum(px, sc)
+    M = np.stack([psum(p2, ss), psum(p2, sc), psum(px, ss), pxsc,
+                  psum(p2, cc), pxsc, psum(px, cc),
+                  psum(x2, ss), psum(x2, sc), psum(x2, cc)], axis=-1)
+    N = np.stack([psum(fp, sr), psum(fp, cr), psum(fx, sr), psum(fx, cr)],
+                 axis=-1)
+    return M, N
+
+
+def _fe_ldl(M):
+    """Unpivoted LDL^T of the 4x4 matrices M (..., 10): the six unit-lower
+    entries (l10, l20, l30, l21, l31, l32) and the pivots d (..., 4).
+    Nothing is rejected: a zero or negative pivot gives what the
+    arithmetic gives (inf / nan / a negative d)."""
+    m00, m01, m02, m03, m11, m12, m13, m22, m23, m33 = (
+        M[..., i] for i in range(10))
+    with np.errstate(all="ignore"):
+        d0 = m00
+        l10, l20, l30 = m01 / d0, m02 / d0, m03 / d0
+        d1 = m11 - l10 * m01
+        t21 = m12 - l20 * m01
+        t31 = m13 - l30 * m01
+        l21, l31 = t21 / d1, t31 / d1
+        d2 = m22 - l20 * m02 - l21 * t21
+        t32 = m23 - l30 * m02 - l31 * t21
+        l32 = t32 / d2
+        d3 = m33 - l30 * m03 - l31 * t31 - l32 * t32
+    return (l10, l20, l30, l21, l31, l32), np.stack([d0, d1, d2, d3], axis=-1)
+
+
+def _fe_solve(low, d, N):
+    """Forward solve z = L^-1 N, fe = 1/2 sum z_j^2 / d_j and the back
+    substitution a = L^-T D^-1 z; N (..., 4), ``low`` and ``d`` from
+    ``_fe_ldl`` (broadcast against N's leading axes)."""
+    l10, l20, l30, l21, l31, l32 = low
+    with np.errstate(all="ignore"):
+        z0 = N[..., 0]
+        z1 = N[..., 1] - l10 * z0
+        z2 = N[..., 2] - l20 * z0 - l21 * z1
+        z3 = N[..., 3] - l30 * z0 - l31 * z1 - l32 * z2
+        y = [z0 / d[..., 0], z1 / d[..., 1], z2 / d[..., 2], z3 / d[..., 3]]
+        fe = (z0 * y[0] + z1 * y[1] + z2 * y[2] + z3 * y[3]) / 2
+        a3 = y[3]
+        a2 = y[2] - l32 * a3
+        a1 = y[1] - l21 * a2 - l31 * a3
+        a0 = y[0] - l10 * a1 - l20 * a2 - l30 * a3
+    return fe, np.stack([a0, a1, a2, a3], axis=-1)
+
+
+def fe_points(prods, ant):
+    """Fe, the maximum-likelihood amplitudes a = M^-1 N and the four
+    pivot ratios d_j / M_jj of every point -> ``(fe (D, nsky, F), amps
+    (D, nsky, F, 4), ratio (D, nsky, F, 4))``.  No pivot rule is applied;
+    the ratios let a test say on which side of the kernels' rule
+    (``d_j > 1e-12 M_jj``) a point lies."""
+    M, N = fe_sums(prods, ant)
+    low, d = _fe_ldl(M)
+    fe, amps = _fe_solve(low, d, N)
+    with np.errstate(all="ignore"):
+        ratio = d / M[..., [0, 4, 7, 9]]
+    return fe, amps, ratio
+
+
+def fe_null_products(prods, z):
+    """Noise-only data products n = L_p z_p (D, F, P, 2, R), with L_p the
+    2x2 Cholesky factor of [[ss, sc], [sc, cc]]_p and ``z``
+    (D, F, P, 2, R)."""
+    prods, z = _ld(prods), _ld(z)
+    ss, cc, sc = (np.moveaxis(prods[:, :, i], 0, 2) for i in (0, 1, 2))
+    assert (ss > 0).all()
+    l00 = np.sqrt(ss)
+    l10 = sc / l00
+    schur = cc - l10 * l10
+    assert (schur > 0).all()
+    l11 = np.sqrt(schur)  # (D, F, P)
+    z0, z1 = z[:, :, :, 0], z[:, :, :, 1]  # (D, F, P, R)
+    return np.stack([l00[..., None] * z0,
+                     l10[..., None] * z0 + l11[..., None] * z1], axis=3)
+
+
+def fe_null_map(prods, ant, n):
+    """The Fe map of every realisation (R, D, nsky, F) from the data
+    products ``n`` (D, F, P, 2, R) (fp64 or longdouble, taken as exact)
+    in place of the planes sr, cr."""
+    n = np.asarray(n, dtype=LD)
+    ant_ld = _ld(ant)
+    M, _ = fe_sums(prods, ant)
+    low, d = _fe_ldl(M)  # (D, nsky, F)
+    D, F, P, _, R = n.shape
+    ns = np.moveaxis(n[:, :, :, 0], 2, 0).reshape(P, D * F * R)
+    nc = np.moveaxis(n[:, :, :, 1], 2, 0).reshape(P, D * F * R)
+
+    def psum(coeff, q):  # -> (D, nsky, F, R)
+        return np.moveaxis((coeff @ q).reshape(-1, D, F, R), 0, 1)
+
+    fp, fx = ant_ld[:, :, 0], ant_ld[:, :, 1]
+    N = np.stack([psum(fp, ns), psum(fp, nc), psum(fx, ns), psum(fx, nc)],
+                 axis=-1)  # (D, nsky, F, R, 4)
+    fe, _ = _fe_solve([x[..., None] for x in low], d[..., None, :], N)
+    return np.moveaxis(fe, 3, 0)
+
+
+def fe_null_data(white, rhs, X):
+    """Joint null data ``white[p, r, 2f+c] - sum_k rhs[p, k, 2f+c]
+    X[p, d, k, r]`` in the (D, F, P, 2, R) layout.  ``white``
+    (P, Rp >= R, ldw >= 2F), ``rhs`` (P, mp, 2F+1), ``X`` (P, D, mp, R);
+    only the entries of the formula are read."""
+    X = np.asarray(X, dtype=np.float64)
+    P, D, mp, R = X.shape
+    F = (rhs.shape[2] - 1) // 2
+    w = _ld(np.asarray(white)[:, :R, :2 * F])
+    B = _ld(np.asarray(rhs)[:, :, :2 * F])
+    X = X.astype(LD)
+    out = np.empty((D, F, P, 2, R), dtype=LD)
+    for p in range(P):
+        for d in range(D):
+            nd = w[p].T - B[p].T @ X[p, d]  # (2F, R)
+            out[d, :, p] = nd.reshape(F, 2, R)
+    return out
+
+
+# ----------------------------------------------------------------------
 # error measure and the tolerance rule
 # ----------------------------------------------------------------------
 def nerr(got, ref):
@@ -327,6 +468,72 @@ def gen_blocks(rng, sizes, log10_ecorr=-6.4):
         for o, sz in zip(offsets, sizes)
     ])
     return uvec, beta, offsets, sizes
+
+
+def gen_fe_case(rng, P, D, F, nsky, delta=None, rows=None):
+    """(prods (P, D, 5, F), ant (nsky, P, 2)) in fp64, the synthetic
+    products of the Fe tests: ss, cc ~ U(1, 2), sc = 0.1 N(0, 1), sr, cr
+    ~ N(0, 1) and a normal antenna table, so every M is a sum of
+    independent positive-definite terms.
+
+    With ``delta`` the sky rows ``rows`` (all rows if ``None``) get
+    ``Fx = 2 F+ + delta g``, g ~ N(0, 1): M is singular at delta = 0 and
+    its two last pivots shrink like delta^2.  ``delta`` is a scalar or
+    one value per entry of ``rows``."""
+    prods = np.empty((P, D, 5, F))
+    prods[:, :, 0:2] = rng.uniform(1.0, 2.0, (P, D, 2, F))
+    prods[:, :, 2] = 0.1 * rng.normal(size=(P, D, F))
+    prods[:, :, 3:] = rng.normal(size=(P, D, 2, F))
+    ant = rng.normal(size=(nsky, P, 2))
+    if delta is not None:
+        rows = np.arange(nsky) if rows is None else np.asarray(rows)
+        delta = np.broadcast_to(np.asarray(delta, dtype=np.float64),
+                                rows.shape)
+        g = rng.normal(size=(len(rows), P))
+        ant[rows, :, 1] = 2.0 * ant[rows, :, 0] + delta[:, None] * g
+    return prods, ant
+
+
+def amp_err(got, ref):
+    """Amplitude error (docs/VALIDATION.md): max|da| / max|a| per point,
+    the largest over the points; ``got`` and ``ref`` (..., 4)."""
+    ref = np.asarray(ref, dtype=LD)
+    d = np.abs(np.asarray(got).astype(LD) - ref).max(axis=-1)
+    q = d / np.abs(ref).max(axis=-1)
+    return float(q.max()) if np.isfinite(q).all() else float("inf")
+
+
+def gen_null_data(rng, P, D, F, m, mp, R, wide=False):
+    """(white (P, Rp, ldw), rhs (P, mp, 2F+1), X (P, D, mp, R)) of
+    ``fe_null_data`` with NaN in everything that must not be read: the
+    last column of rhs, the columns >= 2F and the rows >= R of white.
+    X has zero padding rows m..mp.  Rp = pad16(R) and ldw = 2F + 1 as the
+    engine allocates them; ``wide``: ldw = 2F + 3 and 16 more rows."""
+    Rp = (R + 15) // 16 * 16 + (16 if wide else 0)
+    ldw = 2 * F + (3 if wide else 1)
+    white = np.full((P, Rp, ldw), np.nan)
+    white[:, :R, :2 * F] = rng.normal(size=(P, R, 2 * F))
+    rhs = np.full((P, mp, 2 * F + 1), np.nan)
+    rhs[:, :, :2 * F] = rng.normal(size=(P, mp, 2 * F))
+    X = np.zeros((P, D, mp, R))
+    X[:, :, :m] = rng.normal(size=(P, D, m, R))
+    return white, rhs, X
+
+
+def null_data64(white, rhs, X):
+    """The plain fp64 einsum of ``fe_null_data`` and the componentwise
+    forward bound of its length-mp dot products without the leading
+    ``4 mp eps``: ``|white| + |B|^T |X|``, both (D, F, P, 2, R)."""
+    P, D, mp, R = X.shape
+    F = (rhs.shape[2] - 1) // 2
+    B = rhs[:, :, :2 * F]
+    w = white[:, :R, :2 * F].transpose(0, 2, 1)[:, None]  # (P, 1, 2F, R)
+
+    def lay(a):
+        return a.reshape(P, D, F, 2, R).transpose(1, 2, 0, 3, 4)
+
+    return (lay(w - np.einsum("pkj,pdkr->pdjr", B, X)),
+            lay(np.abs(w) + np.einsum("pkj,pdkr->pdjr", np.abs(B), np.abs(X))))
 
 
 # ----------------------------------------------------------------------
@@ -447,3 +654,187 @@ def block_inverses64(L64):
         _cpu_fsub64(np.tril(L64[k:k + 16, k:k + 16]), eye)
         for k in range(0, L64.shape[0], 16)
     ])
+
+
+# ----------------------------------------------------------------------
+# Fe cases: inputs, the oracle's planes and the host fp64 planes
+# ----------------------------------------------------------------------
+def fe_host(prods, ant):
+    """The host fp64 path of the project on the same inputs:
+    ``festat._assemble_fe_draws`` per sky row -> ``(fe (D, nsky, F),
+    amps (D, nsky, F, 4))``.  Its error against the oracle is the
+    ``base`` of every Fe tolerance."""
+    from fastfp_amd.festat import _assemble_fe_draws
+
+    out = [_assemble_fe_draws(prods, ant[k, :, 0], ant[k, :, 1],
+                              amplitudes=True) for k in range(ant.shape[0])]
+    return (np.stack([o[0] for o in out], axis=1),
+            np.stack([o[1] for o in out], axis=1))
+
+
+def _fe_case(prods, ant, **kw):
+    fe, amps, ratio = fe_points(prods, ant)
+    fe64, amps64 = fe_host(prods, ant)
+    P, D, _, F = prods.shape
+    return Case(P=P, D=D, F=F, nsky=ant.shape[0], prods=prods, ant=ant,
+                fe=fe, amps=amps, ratio=ratio, fe64=fe64, amps64=amps64, **kw)
+
+
+_FE_CASES = {}
+
+
+def fe_case(P, D, F, nsky, seed=0):
+    """One well-conditioned ``gen_fe_case`` with its references.
+
+    Fields: prods, ant, the oracle's fe (D, nsky, F), amps and ratio
+    (D, nsky, F, 4), and the host's fe64, amps64."""
+    key = (P, D, F, nsky, seed)
+    if key not in _FE_CASES:
+        rng = np.random.default_rng([seed, P, D, F, nsky])
+        _FE_CASES[key] = _fe_case(*gen_fe_case(rng, P, D, F, nsky))
+    return _FE_CASES[key]
+
+
+# The conditioning ladder: D = 2, F = 9, nsky = 20, four sky rows per
+# rung; rows 16, 17 lie far below the kernels' pivot rule, rows 18, 19
+# are untouched.  P = 2 has no 1e-3 / 1e-4 rungs (its fourth pivot is
+# already at 1e-13 M_33 there): rows 8..15 stay untouched.  With these
+# seeds every kept point has all pivot ratios >= 1e-10 and every skipped
+# one a ratio < 1e-14 (tests/test_hpref.py), two decades on either side
+# of the kernels' 1e-12 rule.
+LADDER_P = (2, 3, 5, 8, 67)
+LADDER_SKIP = (16, 17)
+LADDER_KEEP_MIN, LADDER_SKIP_MAX = 1e-10, 1e-14
+_LADDER_CASES = {}
+
+
+def ladder_rungs(P):
+    """{delta or None: sky rows} of the kept rungs of the ladder case."""
+    if P == 2:
+        return {1e-1: range(0, 4), 1e-2: range(4, 8),
+                None: list(range(8, 16)) + [18, 19]}
+    return {1e-1: range(0, 4), 1e-2: range(4, 8), 1e-3: range(8, 12),
+            1e-4: range(12, 16), None: [18, 19]}
+
+
+def fe_ladder_case(P):
+    """The ladder case of ``P`` pulsars with the references of
+    ``fe_case`` and ``rungs`` (``ladder_rungs``), ``keep`` (sky rows the
+    kernels must keep) and ``skip`` (rows they must skip)."""
+    if P not in _LADDER_CASES:
+        rungs = ladder_rungs(P)
+        rows, delta = [], []
+        for dl, rr in rungs.items():
+            if dl is not None:
+                rows += list(rr)
+                delta += [dl] * len(rr)
+        rows += list(LADDER_SKIP)
+        delta += [1e-8] * len(LADDER_SKIP)
+        rng = np.random.default_rng([0, P, 1234])
+        prods, ant = gen_fe_case(rng, P, 2, 9, 20, delta=delta, rows=rows)
+        keep = np.array(sorted(r for rr in rungs.values() for r in rr))
+        _LADDER_CASES[P] = _fe_case(
+            prods, ant, rungs={k: np.array(list(v)) for k, v in rungs.items()},
+            keep=keep, skip=np.array(LADDER_SKIP))
+    return _LADDER_CASES[P]
+
+
+def fe_null_refs(prods, ant, z, rows=None):
+    """References of ``fe_null_skymax`` on the sky rows ``rows`` (all if
+    ``None``), in both modes.  ``z`` (D, F, P, 2, R) standard normals.
+
+    Fields: z, n64 (the oracle's n = L z rounded to fp64: the input of
+    the data mode); per mode ``m`` in ("z", "n"): map_m (R, D, nrows, F)
+    longdouble, max_m / arg_m (R, D, F) from it (the index is into
+    ``rows``), and host_m, the femax of ``festat._null_max_host``."""
+    from fastfp_amd.festat import _null_max_host
+
+    sub = ant if rows is None else ant[np.asarray(rows)]
+    n = fe_null_products(prods, z)
+    n64 = np.ascontiguousarray(n.astype(np.float64))
+    out = dict(z=z, n64=n64)
+    for m, src in (("z", n), ("n", n64)):
+        fmap = fe_null_map(prods, sub, src)
+        out["map_" + m] = fmap
+        out["max_" + m] = fmap.max(axis=2)
+        out["arg_" + m] = fmap.argmax(axis=2)
+    out["host_z"] = _null_max_host(prods, sub, z)[0]
+    out["host_n"] = _null_max_host(prods, sub, n=n64)[0]
+    return Case(**out)
+
+
+_LADDER_NULL = {}
+
+
+def fe_ladder_null(P, R=17):
+    """``fe_null_refs`` of the ladder case over its kept rows."""
+    if (P, R) not in _LADDER_NULL:
+        case = fe_ladder_case(P)
+        z = np.random.default_rng([7, P, R]).standard_normal((2, 9, P, 2, R))
+        _LADDER_NULL[P, R] = fe_null_refs(case.prods, case.ant, z,
+                                          rows=case.keep)
+    return _LADDER_NULL[P, R]
+
+
+_NULL_CASES = {}
+
+
+def fe_null_case(P, D, F, nsky, R, seed=0):
+    """``fe_case(P, D, F, nsky)`` with R realisations -> (case, refs of
+    ``fe_null_refs``)."""
+    key = (P, D, F, nsky, R, seed)
+    if key not in _NULL_CASES:
+        case = fe_case(P, D, F, nsky, seed)
+        rng = np.random.default_rng([seed, P, D, F, nsky, R])
+        z = rng.standard_normal((D, F, P, 2, R))
+        _NULL_CASES[key] = (case, fe_null_refs(case.prods, case.ant, z))
+    return _NULL_CASES[key]
+
+
+# the tie case: P = 9, D = 2, F = 9, nsky = 130; row 70 copied into rows
+# 3, 19, 35 (waves 0, 1, 2 of the first sky round) and 99 (wave 2 of the
+# second; row 70 itself is wave 0 of the second)
+TIE_ROWS = (3, 19, 35, 70, 99)
+_TIE_CASES = {}
+
+
+def fe_tie_case(scaled=True):
+    """(prods, ant, ant2) of the tie case; ``ant2`` is ``ant`` with row 3
+    replaced by a fresh random row.  ``scaled``: sr, cr are a signal of
+    random amplitudes from row 70, a hundred times the unit noise, which
+    makes the equal rows the largest of every column."""
+    if scaled not in _TIE_CASES:
+        P, D, F, nsky = 9, 2, 9, 130
+        rng = np.random.default_rng([0, P, D, F, nsky, 99])
+        prods, ant = gen_fe_case(rng, P, D, F, nsky)
+        for r in TIE_ROWS:
+            ant[r] = ant[70]
+        if scaled:
+            a = rng.normal(size=(D, F, 4))
+            fp, fx = ant[70, :, 0, None, None], ant[70, :, 1, None, None]
+            s = fp * a[..., 0] + fx * a[..., 2]  # (P, D, F)
+            c = fp * a[..., 1] + fx * a[..., 3]
+            ss, cc, sc = prods[:, :, 0], prods[:, :, 1], prods[:, :, 2]
+            prods[:, :, 3] += 100.0 * (ss * s + sc * c)
+            prods[:, :, 4] += 100.0 * (sc * s + cc * c)
+        ant2 = ant.copy()
+        ant2[3] = np.random.default_rng(98).normal(size=(P, 2))
+        for a in (prods, ant, ant2):
+            a.setflags(write=False)
+        _TIE_CASES[scaled] = (prods, ant, ant2)
+    return _TIE_CASES[scaled]
+
+
+# shapes of tests/test_fe_oracle.py; tests/test_hpref.py checks on the
+# CPU that every one of them is far on the kept side of the pivot rule
+FE_SHAPES = [  # (P, D, F, nsky)
+    (2, 1, 1, 1), (3, 1, 16, 16), (4, 3, 5, 17), (5, 1, 17, 64),
+    (7, 3, 11, 65), (8, 2, 8, 81), (9, 5, 7, 130), (12, 1, 33, 65),
+    (13, 2, 17, 15), (76, 1, 3, 65), (77, 3, 5, 17), (248, 1, 17, 65),
+]
+FE_AMP_SHAPES = [(5, 5, 7, 20), (9, 4, 16, 65), (3, 5, 13, 17),
+                 (67, 2, 65, 81)]
+FE_NULL_SHAPES = [  # (P, D, F, nsky, R)
+    (2, 1, 1, 1, 1), (3, 1, 16, 17, 16), (5, 3, 5, 65, 17),
+    (8, 2, 8, 81, 33), (9, 1, 17, 130, 70), (67, 3, 11, 65, 65),
+]

@@ -328,3 +328,221 @@ def test_closure_has_no_cancellation(nbt):
     m1, mp = case.m[1], case.mp
     assert (case.L[2:, m1:, m1:] == np.eye(mp - m1)).all()
     assert (case.L[2:, m1:, :m1] == 0).all()
+
+
+# ----------------------------------------------------------------------
+# the Fe oracle: fe_points / fe_null_data vs mpmath, the host fp64 paths
+# vs the oracle (the ``base`` of tests/test_fe_oracle.py), the classes of
+# the conditioning ladder
+# ----------------------------------------------------------------------
+def _mp_fe_point(prods, ant_row, d, f):
+    """(fe, a (4,), ratio (4,), cond) of one point in mpmath, by a route
+    of its own: M and N summed entry by entry, a from an LU solve,
+    fe = 1/2 N.a, the pivots as the squared Cholesky diagonal."""
+    P = prods.shape[0]
+    G = [[mpmath.mpf(float(prods[p, d, 0, f])),
+          mpmath.mpf(float(prods[p, d, 2, f])),
+          mpmath.mpf(float(prods[p, d, 1, f]))] for p in range(P)]
+    M = mpmath.zeros(4, 4)
+    N = mpmath.zeros(4, 1)
+    for p in range(P):
+        ss, sc, cc = G[p]
+        blk = [[ss, sc], [sc, cc]]
+        co = [mpmath.mpf(float(ant_row[p, 0])),
+              mpmath.mpf(float(ant_row[p, 1]))]
+        dat = [mpmath.mpf(float(prods[p, d, 3, f])),
+               mpmath.mpf(float(prods[p, d, 4, f]))]
+        for i in range(4):
+            N[i] += co[i // 2] * dat[i % 2]
+            for j in range(4):
+                M[i, j] += co[i // 2] * co[j // 2] * blk[i % 2][j % 2]
+    a = mpmath.lu_solve(M, N)
+    fe = sum(N[i] * a[i] for i in range(4)) / 2
+    L = mpmath.cholesky(M)
+    ratio = [L[j, j] ** 2 / M[j, j] for j in range(4)]
+    M64 = np.array([[float(M[i, j]) for j in range(4)] for i in range(4)])
+    return fe, [a[i] for i in range(4)], ratio, float(np.linalg.cond(M64))
+
+
+@pytest.mark.parametrize("P", [3, 5])
+def test_fe_points_vs_mpmath(P):
+    """Random table (rows 18, 19) and the 1e-3 rung (rows 8, 9) of the
+    ladder case.  The 8-ulp rule of ``_assert_ulps`` is relative to a
+    well-conditioned plane; here it is scaled by cond(M) of the point,
+    computed from the mpmath M."""
+    case = hpref.fe_ladder_case(P)
+    for sky in (18, 19, 8, 9):
+        for d, f in ((0, 0), (1, 8)):
+            fe, a, ratio, cond = _mp_fe_point(case.prods, case.ant[sky], d, f)
+            lim = 8 * ULP * cond
+            e_fe = abs(_mp(case.fe[d, sky, f]) - fe) / abs(fe)
+            amax = max(abs(x) for x in a)
+            e_a = max(abs(_mp(g) - w) for g, w in
+                      zip(case.amps[d, sky, f], a)) / amax
+            e_r = max(abs(_mp(g) - w) for g, w in
+                      zip(case.ratio[d, sky, f], ratio))
+            print(f"P={P} sky={sky} ({d},{f}): cond {cond:.2e} fe "
+                  f"{float(e_fe) / ULP:.1f} amps {float(e_a) / ULP:.1f} "
+                  f"ratio {float(e_r) / ULP:.1f} ulp")
+            assert e_fe <= lim and e_a <= lim and e_r <= lim
+
+
+def test_fe_sums_layout():
+    """The ten M entries are those of ``festat._moments`` and the four N
+    sums those of ``_assemble_fe_draws``, in their order."""
+    from fastfp_amd.festat import _moments, _psum
+
+    case = hpref.fe_case(5, 3, 5, 17)
+    M, N = hpref.fe_sums(case.prods, case.ant)
+    assert M.shape == (3, 17, 5, 10) and N.shape == (3, 17, 5, 4)
+    assert M.dtype == LD and N.dtype == LD
+    for k in (0, 16):
+        fplus, fcross = case.ant[k, :, 0], case.ant[k, :, 1]
+        for i, m in enumerate(_moments(case.prods, fplus, fcross)):
+            assert hpref.nerr(m, M[:, k, :, i]) < AGREE
+        sr, cr = case.prods[:, :, 3], case.prods[:, :, 4]
+        for i, n in enumerate([_psum(fplus, sr), _psum(fplus, cr),
+                               _psum(fcross, sr), _psum(fcross, cr)]):
+            assert hpref.nerr(n, N[:, k, :, i]) < AGREE
+
+
+def test_fe_null_data_vs_mpmath():
+    rng = np.random.default_rng(41)
+    P, D, F, mp, R = 2, 2, 2, 16, 3
+    white, rhs, X = hpref.gen_null_data(rng, P, D, F, 11, mp, R, wide=True)
+    got = hpref.fe_null_data(white, rhs, X)
+    assert got.shape == (D, F, P, 2, R) and got.dtype == LD
+    want = np.empty(got.shape, dtype=object)
+    for d, f, p, c, r in np.ndindex(got.shape):
+        acc = mpmath.mpf(float(white[p, r, 2 * f + c]))
+        for k in range(mp):
+            acc -= (mpmath.mpf(float(rhs[p, k, 2 * f + c]))
+                    * mpmath.mpf(float(X[p, d, k, r])))
+        want[d, f, p, c, r] = acc
+    _assert_ulps(got, want, "fe_null_data")
+    # and the fp64 einsum the GPU test takes its base from
+    e64, mag = hpref.null_data64(white, rhs, X)
+    assert hpref.nerr(e64, got) < AGREE
+    assert (np.abs(got) <= mag).all()
+
+
+def test_fe_null_products_and_map():
+    """n = L z against ``festat._null_draws``; the null map with the data
+    planes themselves as n is the Fe map."""
+    from fastfp_amd.festat import _null_draws
+
+    case, refs = hpref.fe_null_case(5, 3, 5, 65, 17)
+    n = hpref.fe_null_products(case.prods, refs.z)
+    ns, nc = _null_draws(case.prods, refs.z)  # (P, D, F, R)
+    assert hpref.nerr(np.moveaxis(ns, 0, 2), n[:, :, :, 0]) < AGREE
+    assert hpref.nerr(np.moveaxis(nc, 0, 2), n[:, :, :, 1]) < AGREE
+    assert refs.map_z.shape == (17, 3, 65, 5)
+    data = case.prods[:, :, 3:].transpose(1, 3, 0, 2)[..., None]
+    assert data.shape == (3, 5, 5, 2, 1)  # (D, F, P, 2, R = 1)
+    fmap = hpref.fe_null_map(case.prods, case.ant, data)
+    assert hpref.nerr(fmap[0], case.fe) < 8 * ULP
+
+
+@pytest.mark.parametrize("P", hpref.LADDER_P)
+def test_fe_host_base_per_rung(P):
+    """The errors of the host fp64 paths against the oracle, one plane
+    per rung: the ``base`` of the device tolerances.  Only finiteness is
+    asserted, and 64 eps on the untouched rows (for P >= 3: the
+    untouched rows of P = 2 reach cond(M) ~ 1e3 and are no
+    well-conditioned rung)."""
+    case = hpref.fe_ladder_case(P)
+    for dl, rows in case.rungs.items():
+        b_fe = hpref.nerr(case.fe64[:, rows], case.fe[:, rows])
+        b_a = hpref.amp_err(case.amps64[:, rows], case.amps[:, rows])
+        print(f"P={P} delta={dl}: host fe {b_fe:.3e} amps {b_a:.3e}")
+        assert np.isfinite(b_fe) and np.isfinite(b_a)
+        if dl is None and P >= 3:
+            assert b_fe < 64 * hpref.EPS64 and b_a < 64 * hpref.EPS64
+    refs = hpref.fe_ladder_null(P)
+    for m in ("z", "n"):
+        b = hpref.nerr(getattr(refs, "host_" + m), getattr(refs, "max_" + m))
+        print(f"P={P} null maxima over the kept rows, mode {m}: host {b:.3e}")
+        assert np.isfinite(b)
+
+
+def test_fe_host_base_well_conditioned():
+    worst = 0.0
+    for shape in hpref.FE_SHAPES[:-1] + hpref.FE_AMP_SHAPES:
+        case = hpref.fe_case(*shape)
+        b_fe = hpref.nerr(case.fe64, case.fe)
+        b_a = hpref.amp_err(case.amps64, case.amps)
+        print(f"{shape}: host fe {b_fe:.3e} amps {b_a:.3e} smallest pivot "
+              f"ratio {float(case.ratio.min()):.2e}")
+        assert np.isfinite(b_fe) and np.isfinite(b_a)
+        assert case.ratio.min() >= hpref.LADDER_KEEP_MIN
+        if shape[0] >= 3:
+            worst = max(worst, b_fe)
+    assert worst < 64 * hpref.EPS64
+    for shape in hpref.FE_NULL_SHAPES[:3]:
+        case, refs = hpref.fe_null_case(*shape)
+        assert case.ratio.min() >= hpref.LADDER_KEEP_MIN
+        for m in ("z", "n"):
+            b = hpref.nerr(getattr(refs, "host_" + m),
+                           getattr(refs, "max_" + m))
+            print(f"{shape} null mode {m}: host {b:.3e}")
+            assert np.isfinite(b)
+            if shape[0] >= 3:
+                assert b < 64 * hpref.EPS64
+    # the fp64 einsum of the null data
+    rng = np.random.default_rng(43)
+    white, rhs, X = hpref.gen_null_data(rng, 2, 2, 33, 43, 48, 65, wide=True)
+    e64, _ = hpref.null_data64(white, rhs, X)
+    b = hpref.nerr(e64, hpref.fe_null_data(white, rhs, X))
+    print(f"null data, fp64 einsum: {b:.3e}")
+    assert b < 64 * hpref.EPS64
+
+
+@pytest.mark.parametrize("P", hpref.LADDER_P)
+def test_fe_ladder_classes(P):
+    """Every kept point has all four oracle pivot ratios >= 1e-10, every
+    point of rows 16, 17 a smallest ratio < 1e-14, and nothing lies
+    between: the kernels' 1e-12 rule is two decades from either class,
+    so a device point may never be on the other side of it."""
+    case = hpref.fe_ladder_case(P)
+    assert sorted(list(case.keep) + list(case.skip)) == list(range(20))
+    smallest = case.ratio.min(axis=-1)  # (D, nsky, F)
+    assert np.isfinite(case.ratio.astype(np.float64)).all()
+    for dl, rows in case.rungs.items():
+        print(f"P={P} delta={dl}: smallest ratio "
+              f"{float(smallest[:, rows].min()):.2e}")
+    print(f"P={P} skipped rows: largest smallest ratio "
+          f"{float(smallest[:, case.skip].max()):.2e}")
+    assert (smallest[:, case.keep] >= hpref.LADDER_KEEP_MIN).all()
+    assert (smallest[:, case.skip] < hpref.LADDER_SKIP_MAX).all()
+    between = (smallest < hpref.LADDER_KEEP_MIN) \
+        & (smallest >= hpref.LADDER_SKIP_MAX)
+    assert not between.any()
+
+
+def test_fe_tie_case_margin():
+    """The five equal rows of the tie case are the largest of every
+    column of the oracle's map, by 5 % at least: eleven orders above the
+    device tolerance (16 * 64 eps), so no rounding decides between a tie
+    row and another row.
+
+    A factor of 4 is out of reach on a random antenna table: a signal
+    from row 70 lies in span(F+, Fx)_70 (x) R^2 of the 2 P = 18 data
+    dimensions, another row recovers on average the share 2 / P = 0.22
+    of it, and the largest share among 125 random rows is near 0.9
+    whatever amplitudes the signal has."""
+    prods, ant, ant2 = hpref.fe_tie_case()
+    fe, _, ratio = hpref.fe_points(prods, ant)
+    assert ratio.min() >= hpref.LADDER_KEEP_MIN
+    ties = list(hpref.TIE_ROWS)
+    for r in ties:
+        assert (fe[:, r] == fe[:, 70]).all()
+    others = np.setdiff1d(np.arange(130), ties)
+    margin = (fe[:, 70][:, None] / fe[:, others]).min()
+    print(f"tie rows over the best other row: factor {float(margin):.3f}")
+    assert margin > 1.05
+    assert (fe.argmax(axis=1) == 3).all()
+    fe2, _, _ = hpref.fe_points(prods, ant2)
+    margin2 = (fe2[:, 70] / fe2[:, 3]).min()
+    print(f"tie rows over the replaced row 3: factor {float(margin2):.3f}")
+    assert margin2 > 1.05
+    assert (fe2.argmax(axis=1) == 19).all()
